@@ -1,9 +1,18 @@
 #!/usr/bin/env python
 """bench.py -- frames/sec of the Imitator.forward() hot path on MI355X (BASELINE.json's metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times ONE window of exactly `--steps` steps, writes the outputs if asked and prints the
+line: `value` (frames/s), `ms_per_step`, `dtype` and the configuration.  Everything else the line can carry -- the repeated
+windows, clocks, roofline, exact-fp32 pass, strict windows, CPU baseline + parity, per-rank block, `secondary` -- is
+measured only with `--full` (the `--no-*` switches then leave parts of it out).
+
+--dump-outputs DIR: after the timed windows, the frames the last timed step computed -- what Imitator.predict_batches
+yields to its caller for that batch, (8, 3, 256, 256) float32 in [-1, 1] -- are written to DIR/preds.npy (rank 0's).  The
+inputs are synthetic and seeded: the same arguments give the same frames, so two builds can be compared output for output.
 
 A "step" is one pass of the hot path over one batch of 8 synthetic 256x256 target frames of ONE personalised
 source (BASELINE.json configs[1]): camera policy -> SMPL vertices -> project/rasterise -> cond, flow T, warped
@@ -12,16 +21,16 @@ background blend.  Inputs (SMPL vectors, source image, cached source features) a
 region; the per-batch device->host copy of the result is outside it.  Every rank runs the same per-GPU work on its
 own frames (weak scaling, no data-path collective).
 
-Launching.  `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment re-executes itself under
-`python -m torch.distributed.run --nproc-per-node N` (one rank per GPU, RCCL); if fewer than N devices are visible it exits 1 instead
-of measuring one GPU and printing `n_gpus: 1`.  A WORLD_SIZE that disagrees with --gpus is an error, too.
+Launching.  `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment runs itself again under
+`python -m torch.distributed.run --nproc-per-node N` (one rank per GPU, RCCL) as a child process; if fewer than N devices are
+visible it exits 1 instead of measuring one GPU and printing `n_gpus: 1`.  A WORLD_SIZE that disagrees with --gpus is an error, too.
 
-Timing.  After the warm-up the `--steps` window is timed `--repeats` times (default 5), every window bracketed by a barrier and a
-device synchronisation on both sides and reduced with MAX over the ranks; `ms_per_step` / `value` are the MEDIAN window, the line
-also carries `ms_per_step_min/max`, the per-window list and the GPU's clock / power sampled (amdsmi) while the windows ran -- the part
-is power-limited and boxes differ by +-5 %, a single 45 ms window is as noisy as a round's gain.
+Timing.  After the warm-up the `--steps` window is timed `--repeats` times (default 1; 5 with --full), every window bracketed by a
+barrier and a device synchronisation on both sides and reduced with MAX over the ranks; `ms_per_step` / `value` are the MEDIAN window,
+the line also carries `ms_per_step_min/max` and the per-window list; with --full also the GPU's clock / power sampled (amdsmi) while
+the windows ran -- the part is power-limited and boxes differ by +-5 %, a single 45 ms window is as noisy as a round's gain.
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  Besides the contract fields it carries (all but `rccl` with --full only)
   roofline     : the dominant implicit-GEMM conv kernel, algorithmic FLOP / HIP-event time of its launches, as a
                  fraction of the MFMA peak both ways (algorithmic and executed products); exact_fp32_mode has its own
   cpu_baseline : the CPU oracle (port of the reference's PyTorch path + C rasteriser) timed on this box's host cores
@@ -43,6 +52,8 @@ Rank 0 prints ONE JSON line.  Besides the contract fields it carries
 import argparse
 import json
 import os
+import signal
+import subprocess
 import sys
 import time
 
@@ -94,11 +105,18 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=100)
     p.add_argument("--warmup", type=int, default=10)
-    p.add_argument("--repeats", type=int, default=5,
-                   help="timed windows of --steps steps each; the line reports the median window (min / max beside it)")
-    p.add_argument("--settle-ms", type=float, default=300.0,
+    p.add_argument("--full", action="store_true",
+                   help="also measure and check everything besides the headline figure (repeated windows, clocks, roofline, "
+                        "exact-fp32 pass, strict windows, CPU baseline + parity, per-rank block, secondary workloads)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the frames of the last timed step to DIR/preds.npy (float32)")
+    p.add_argument("--repeats", type=int, default=None,
+                   help="timed windows of --steps steps each (default 1; 5 with --full); the line reports the median window "
+                        "(min / max beside it)")
+    p.add_argument("--settle-ms", type=float, default=1000.0,
                    help="untimed steps before the warm-up until this much wall time has passed (DVFS: the first ~100 ms "
-                        "after idle run ~15%% slower); 0 disables")
+                        "after idle run ~15%% slower, and a plain run's one window has no median to hide a slow start); "
+                        "0 disables")
     p.add_argument("--frames", type=int, default=1024, help="length of the synthetic reference sequence")
     p.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU oracle timing (profiling runs)")
     p.add_argument("--no-roofline", action="store_true", help="skip the HIP-event pass over the conv kernel")
@@ -111,13 +129,18 @@ def parse():
                    help="skip the `secondary` block (appearance transfer = BASELINE config 4, training iteration = config 5)")
     p.add_argument("--lanes", type=int, default=None,
                    help="generator engines/streams consecutive batches are dealt to (default: Imitator.lanes = 2)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    return args
 
 
 def self_launch(args):
-    """`python bench.py --gpus N` (N > 1) started bare, i.e. without torch.distributed.run's environment: re-execute under it, one
-    rank per GPU.  With fewer than N visible devices the run is refused (exit 1) -- it would otherwise measure ONE GPU.  Test hook:
-    LWG_DIST_BACKEND=gloo lets the N ranks share the visible device(s) (RCCL wants a GPU per rank)."""
+    """`python bench.py --gpus N` (N > 1) started bare, i.e. without torch.distributed.run's environment: run again under it, one
+    rank per GPU, as a CHILD process, and exit with its status.  (Not an exec: counting the devices has already initialised the
+    GPU runtime in this process, and a process with the GPU open must not replace its program.)  With fewer than N visible devices
+    the run is refused (exit 1) -- it would otherwise measure ONE GPU.  Test hook: LWG_DIST_BACKEND=gloo lets the N ranks share the
+    visible device(s) (RCCL wants a GPU per rank)."""
     ndev = torch.cuda.device_count() if torch.cuda.is_available() else 0
     shared = os.environ.get("LWG_DIST_BACKEND") == "gloo" and ndev >= 1
     if ndev < args.gpus and not shared:
@@ -134,7 +157,12 @@ def self_launch(args):
     sys.stderr.write("bench.py: --gpus %d without a torch.distributed environment: launching %s\n" % (args.gpus, " ".join(cmd[1:8])))
     sys.stderr.flush()
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"), LWG_SELF_LAUNCHED="1")
-    os.execve(sys.executable, cmd, env)
+    child = subprocess.Popen(cmd, env=env)
+    for sig in (signal.SIGTERM, signal.SIGINT):
+        # a stop request reaches the launcher, which stops its ranks; this process waits for them
+        signal.signal(sig, lambda signum, frame: child.send_signal(signum))
+    rc = child.wait()
+    sys.exit(rc if rc >= 0 else 128 - rc)
 
 
 class GpuSampler:
@@ -556,7 +584,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X: the hot path has no CPU fallback")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        self_launch(args)          # does not return: re-executes under torch.distributed.run, or exits 1
+        self_launch(args)          # does not return: runs the ranks under torch.distributed.run and exits with its status, or exits 1
     if int(os.environ.get("WORLD_SIZE", 1)) != args.gpus:
         # never a line whose n_gpus differs from what was asked for
         raise SystemExit("bench.py: --gpus %d but WORLD_SIZE=%s: launch with --nproc-per-node %d (or bare, bench.py starts the "
@@ -601,12 +629,14 @@ def main():
         torch.cuda.synchronize(dev)
     run_steps(0, args.warmup)
     sharding.barrier(dev)
-    # host cost of enqueueing a step, measured on a short burst into empty queues (over hundreds of steps the host
-    # simply blocks on the full launch queue, which says nothing)
-    th = time.perf_counter()
-    run_steps(0, 4)
-    host_dt = (time.perf_counter() - th) / 4 * args.steps
-    sharding.barrier(dev)
+    host_dt = None
+    if args.full:
+        # host cost of enqueueing a step, measured on a short burst into empty queues (over hundreds of steps the host
+        # simply blocks on the full launch queue, which says nothing)
+        th = time.perf_counter()
+        run_steps(0, 4)
+        host_dt = (time.perf_counter() - th) / 4 * args.steps
+        sharding.barrier(dev)
     rdev = dev if torch.distributed.is_initialized() else "cpu"   # RCCL reduces device tensors
 
     def timed_window(first, everyone=True):
@@ -626,27 +656,34 @@ def main():
         return sharding.max_over_ranks(time.perf_counter() - t0, rdev), mine, o
 
     single_rank_fps = None
-    if world > 1:
+    if world > 1 and args.full:
         # rank 0 runs one window ALONE (the others wait at the barrier below): the single-GPU rate of this very run, the
         # denominator of `linear_frac`
         if rank == 0:
             solo, _, _ = timed_window(args.warmup, everyone=False)
             single_rank_fps = BATCH * args.steps / solo
         sharding.barrier(dev)
-    sampler = GpuSampler(local_rank)
-    sampler.start()
+    sampler = GpuSampler(local_rank) if args.full else None
+    if sampler is not None:
+        sampler.start()
     windows, mine_all, out = [], [], None
     for r in range(max(1, args.repeats)):
         w, mine, out = timed_window(args.warmup + r * args.steps)
         windows.append(w)
         mine_all.append(mine)
-    sampler.stop()
+    if sampler is not None:
+        sampler.stop()
     order = sorted(range(len(windows)), key=lambda i: windows[i])
     med = order[len(order) // 2]
     dt = windows[med]                       # the median window: what `value` and `ms_per_step` report
-    assert bool(torch.isfinite(out).all())
+    # what the caller of the timed path received for the last timed step, copied before anything else runs on the device
+    last = out.float().cpu().numpy()
+    assert bool(np.isfinite(last).all())
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "preds.npy"), last)
     ranks_block = None
-    if world > 1:
+    if world > 1 and args.full:
         # every rank's own completion time of the median window, its device, its clocks: a straggler GPU is visible here
         mine_fps = BATCH * args.steps / mine_all[med]
         gathered = [None] * world
@@ -717,7 +754,7 @@ def main():
                 block["traffic_note"] = "fabric-side bytes per launch, rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, profiles/%s" % TRAFFIC_FILE
         return block
 
-    roofline = roofline_pass() if not args.no_roofline else None
+    roofline = roofline_pass() if args.full and not args.no_roofline else None
     # what carried the barrier / max-over-ranks above (every rank takes part in its one-element all-reduce)
     rccl = sharding.collective_info(dev) if torch.distributed.is_initialized() else None
 
@@ -726,7 +763,7 @@ def main():
         return w[len(w) // 2], w
 
     fp32_mode = None
-    if precision != "fp32" and not args.no_fp32_mode:
+    if args.full and precision != "fp32" and not args.no_fp32_mode:
         # the same steps with the convolutions on the exact-fp32 MFMA path: the reference's own arithmetic (like for like)
         imitator.generator.precision = "fp32"
         run_steps(0, args.warmup)
@@ -742,7 +779,7 @@ def main():
     # the reference's call pattern strictly: ONE batch of 8 per generator launch sequence (models/imitator.py:166-171 runs one
     # forward per batch) -- with the two lanes, and on a single stream
     strict = {}
-    if not args.no_strict:
+    if args.full and not args.no_strict:
         keep = os.environ.get("LWG_FUSE")
         os.environ["LWG_FUSE"] = "1"
         try:
@@ -781,9 +818,10 @@ def main():
             "repeats": len(windows), "ms_per_step_min": round(min(windows) / args.steps * 1e3, 4),
             "ms_per_step_max": round(max(windows) / args.steps * 1e3, 4),
             "ms_per_step_windows": [round(w / args.steps * 1e3, 4) for w in windows],
-            "gpu_clocks": sampler.summary(),
-            "host_enqueue_ms_per_step": round(host_dt / args.steps * 1e3, 4),
         }
+        if args.full:
+            line["gpu_clocks"] = sampler.summary()
+            line["host_enqueue_ms_per_step"] = round(host_dt / args.steps * 1e3, 4)
         if rccl is not None:
             # N > 1 (or LWG_FORCE_DIST=1 at N = 1): the process group behind the timing barrier -- backend 'nccl' IS RCCL on
             # ROCm; `ranks` is the communicator's size as the library reports it, `allreduce_of_ones` must equal it
@@ -795,7 +833,7 @@ def main():
             line["ranks"] = ranks_block   # (distinct_devices is reported, not enforced: device identifiers are the runtime's to define)
         if fp32_mode is not None:
             line["exact_fp32_mode"] = fp32_mode
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"], kept = cpu_baseline()
             # self-check of the timed pipeline against the oracle, after and outside the timed region
             line["parity"] = parity_block(imitator, src_img, bg_img, smpls, lanes, kept)
@@ -813,7 +851,7 @@ def main():
                                  "theta_chain_linf_all": pb["theta_linf_all"],
                                  "theta_chain_fim_mismatch_pixels": pb["theta_fim_mismatch_pixels"]})
             line["roofline"] = roofline
-        if world == 1 and not args.no_secondary:
+        if args.full and world == 1 and not args.no_secondary:
             # other workloads of BASELINE.json, measured after (and outside) the timed region (field definitions: DESIGN.md 5.3)
             line["secondary"] = {"swap": secondary_swap(dev), "latency": secondary_latency(dev),
                                  "personalize": secondary_personalize(dev), "train": secondary_train()}

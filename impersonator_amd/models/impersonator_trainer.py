@@ -292,6 +292,7 @@ class Impersonator(BaseModel):
                 batch = dict(input_G_bg=self._input_G_bg, input_G_src=self._input_G_src, input_G_tsf=self._input_G_tsf, T=self._T,
                              real_src=self._real_src, real_tsf=self._real_tsf, bg_mask=self._bg_mask)
                 torch.cuda.synchronize()
+                sharding.quiesce()          # the eager iterations' collectives: retired before the capture starts
                 graph = torch.cuda.CUDAGraph()
                 # thread_local: ProcessGroupNCCL's watchdog thread polls the events of earlier collectives; under the default
                 # (global) mode such a call from ANOTHER thread while this one captures is an error that kills the process

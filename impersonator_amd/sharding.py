@@ -145,6 +145,15 @@ def collectives_active():
     return dist.is_available() and dist.is_initialized() and (dist.get_world_size() > 1 or forced())
 
 
+def quiesce():
+    """Returns once the RCCL process group's watchdog thread has retired every collective issued so far (no-op without one).
+    Until then that thread queries the HIP events of finished collectives, and c10d rethrows a HIP error there as a process
+    abort: a graph capture that overlaps such a query can end the job.  Call it after a device synchronisation, before
+    capturing."""
+    if dist.is_available() and dist.is_initialized() and dist.get_backend() == "nccl":
+        dist.distributed_c10d._get_default_group()._wait_for_pending_works()
+
+
 def average_gradients(flat_grads):
     """Data-parallel training: averages a flat gradient tensor over the ranks in place (all-reduce SUM
     then divide) -- RCCL over xGMI for CUDA tensors, gloo on CPU.  No-op without an initialised multi-rank group.  The

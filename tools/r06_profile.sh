@@ -3,7 +3,7 @@
 #
 #     gpurun --timeout 2400 -- 'bash tools/r06_profile.sh [TAG]'        # outputs under gpurun_out/TAG/, summaries named r06_*.md
 #
-#   1. bench.py (the driver's default command)                                -> bench.json  (fps, roofline, cpu_baseline, parity, secondary)
+#   1. bench.py --full (the line with every block)                            -> bench.json  (fps, roofline, cpu_baseline, parity, secondary)
 #   2. rocprofv3 --kernel-trace --stats of the bench on ONE lane, bf16x3      -> r06_kernel_stats.md, r06_roofline.md (per layer / per kernel /
 #      and exact fp32                                                            apply launches by position; tools/roofline_from_profiles.py)
 #   3. rocprofv3 --pmc MFMA-busy / clocks (own pass), FETCH_SIZE, WRITE_SIZE  -> r06_pmc_mfma.md, r06_traffic.{md,json}
@@ -18,11 +18,11 @@ O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 T0=$(date +%s)
-timeout 900 python $R/bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$? wall=$(( $(date +%s) - T0 )) s"
+timeout 900 python $R/bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$? wall=$(( $(date +%s) - T0 )) s"
 
-BF="python $R/bench.py --lanes 1 --steps 16 --warmup 4 --repeats 1 --settle-ms 0 --precision bf16x3 --no-cpu-baseline --no-fp32-mode --no-secondary --no-strict"
+BF="python $R/bench.py --full --lanes 1 --steps 16 --warmup 4 --repeats 1 --settle-ms 0 --precision bf16x3 --no-cpu-baseline --no-fp32-mode --no-secondary --no-strict"
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o k -- $BF > $O/stats.log 2>&1
-FP="python $R/bench.py --lanes 1 --steps 8 --warmup 2 --repeats 1 --settle-ms 0 --precision fp32 --no-cpu-baseline --no-secondary --no-strict"
+FP="python $R/bench.py --full --lanes 1 --steps 8 --warmup 2 --repeats 1 --settle-ms 0 --precision fp32 --no-cpu-baseline --no-secondary --no-strict"
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/fp32_stats -o k -- $FP > $O/fp32_stats.log 2>&1
 PM="python $R/bench.py --lanes 1 --steps 2 --warmup 1 --repeats 1 --precision bf16x3 --no-cpu-baseline --no-roofline --no-fp32-mode --no-secondary --no-strict"
 timeout 600 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv \
