@@ -76,6 +76,8 @@ _PROTOS = {
     "lwg_inpaint_missing_weights": (_i, [_vp]),
     "lwg_inpaint_set_precision": (_i, [_vp, _i]),
     "lwg_inpaint_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lwg_inpaint_attention_workspace_bytes": (_c.c_size_t, [_i, _i, _i]),
+    "lwg_inpaint_attention": (_i, [_vp, _vp, _vp, _f, _i, _i, _i, _i, _vp, _vp, _c.c_size_t, _vp]),
     "lwg_conv2d_workspace_bytes": (_c.c_size_t, [_vp]),
     "lwg_conv2d_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _c.c_size_t, _vp]),
     "lwg_conv2d_backward_data": (_i, [_vp, _vp, _vp, _vp, _vp, _c.c_size_t, _vp]),

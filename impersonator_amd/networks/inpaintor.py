@@ -130,10 +130,16 @@ class InpaintSANet(nn.Module):
         """inpaintor.py:178-202 -> (coarse_x, x, comp_imgs) | comp_imgs (only_out) | x (only_x)."""
         if self.training:
             raise RuntimeError("InpaintSANet runs in eval mode only (folded BatchNorm statistics); call .eval()")
+        if imgs.dim() == 4 and imgs.shape[0] != 1:
+            raise ValueError("the inpaintor runs once per source image (batch 1), as models/imitator.py:125 does")
+        # the handle's buffers are sized for image_size: any other tensor would be read or written past its end
+        s = self.image_size
+        if tuple(imgs.shape) != (1, 3, s, s):
+            raise ValueError("InpaintSANet(image_size=%d): imgs must be (1, 3, %d, %d), got %s" % (s, s, s, tuple(imgs.shape)))
+        if tuple(masks.shape) != (1, 1, s, s):
+            raise ValueError("InpaintSANet(image_size=%d): masks must be (1, 1, %d, %d), got %s" % (s, s, s, tuple(masks.shape)))
         if not imgs.is_cuda:
             raise RuntimeError("impersonator_amd runs on the GPU only (got a %s tensor); there is no CPU fallback" % imgs.device)
-        if imgs.shape[0] != 1:
-            raise ValueError("the inpaintor runs once per source image (batch 1), as models/imitator.py:125 does")
         h = self._ensure_handle()
         imgs = imgs.float().contiguous()
         masks = masks.float().contiguous()

@@ -290,6 +290,17 @@ LWG_API int lwg_inpaint_set_precision(lwg_inpaint *g, int precision);
  * coarse_x [optional], x (refined, clamped), comp_imgs = x*masks + imgs*(1-masks) [optional], all (1,3,is,is). */
 LWG_API int lwg_inpaint_forward(lwg_inpaint *g, const float *imgs, const float *masks, float *coarse_x, float *x,
                                 float *comp_imgs, lwg_stream_t stream);
+/* Diagnostic entry (as lwg_generator_peek: for tests, not a hot path): the inpaintor's self-attention alone, through the launch
+ * code lwg_inpaint_forward runs.  out = gamma * softmax((q + b_q)(k + b_k)^T)(v + b_v) + x over N tokens; qkv (N,192): the raw
+ * 1x1-conv output [q 16 | k 16 | v 128 | 32 unused] per token, bias (192) laid out alike, x and out (N,128); all device, 16-byte
+ * aligned.  kernel 0: the streaming vector-ALU kernel (N % 64 == 0).  kernel 1: the matrix-core kernel over key_chunks chunks
+ * of whole 32-key tiles plus the merge (N % 256 == 0, N % (32 key_chunks) == 0); key_chunks 0 = what lwg_inpaint_create picks
+ * for N.  split_out 1 (kernel 1 only): out in the split-bf16 format, per 32 channels [32 bf16 hi | 32 bf16 lo].  workspace
+ * (kernel 1): lwg_inpaint_attention_workspace_bytes, scratch only; kernel 0 takes NULL / 0. */
+LWG_API size_t lwg_inpaint_attention_workspace_bytes(int N, int kernel, int key_chunks);
+LWG_API int lwg_inpaint_attention(const float *qkv, const float *bias, const float *x, float gamma, int N, int kernel,
+                                  int key_chunks, int split_out, float *out, void *workspace, size_t workspace_bytes,
+                                  lwg_stream_t stream);
 
 /* ---- training, first slice: the PatchGAN discriminator update ---------------------------------
  * Replaces PatchDiscriminator.forward (networks/discriminator.py:8-57, norm_type='instance', use_sigmoid=False) and,

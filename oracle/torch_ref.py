@@ -342,19 +342,22 @@ def _gated(x, sd, prefix, spec):
                         sd[prefix + ".batch_norm2d.weight"], sd[prefix + ".batch_norm2d.bias"], False, 0.0, 1e-5)
 
 
-def _self_attention(x, sd, p):
-    """SelfAttention (networks/inpaintor.py:71-107)."""
+def _self_attention(x, sd, p, probe=None):
+    """SelfAttention (networks/inpaintor.py:71-107).  probe: a dict that receives the (tokens, tokens) logits."""
     b, c, w, h = x.shape
     q = F.conv2d(x, sd[p + ".query_conv.weight"], sd[p + ".query_conv.bias"]).view(b, -1, w * h).permute(0, 2, 1)
     k = F.conv2d(x, sd[p + ".key_conv.weight"], sd[p + ".key_conv.bias"]).view(b, -1, w * h)
-    attn = torch.softmax(torch.bmm(q, k), dim=-1)
+    logits = torch.bmm(q, k)
+    if probe is not None:
+        probe["attn_logits"] = logits[0]
+    attn = torch.softmax(logits, dim=-1)
     v = F.conv2d(x, sd[p + ".value_conv.weight"], sd[p + ".value_conv.bias"]).view(b, -1, w * h)
     out = torch.bmm(v, attn.permute(0, 2, 1)).view(b, c, w, h)
     return sd[p + ".gamma"] * out + x
 
 
-def inpaint_forward(sd, imgs, masks, c_dim=4):
-    """InpaintSANet.forward (networks/inpaintor.py:178-202) -> (coarse_x, x, comp_imgs)."""
+def inpaint_forward(sd, imgs, masks, c_dim=4, probe=None):
+    """InpaintSANet.forward (networks/inpaintor.py:178-202) -> (coarse_x, x, comp_imgs).  probe: see _self_attention."""
     coarse, refine_conv, refine_up = inpaint_layers(c_dim)
     x = torch.cat([imgs * (1 - masks) + masks, masks], dim=1)
     for i, spec in enumerate(coarse):
@@ -363,7 +366,7 @@ def inpaint_forward(sd, imgs, masks, c_dim=4):
     x = torch.cat([imgs * (1 - masks) + coarse_x * masks, masks], dim=1)
     for i, spec in enumerate(refine_conv):
         x = _gated(x, sd, "refine_conv_net.%d" % i, spec)
-    x = _self_attention(x, sd, "refine_attn")
+    x = _self_attention(x, sd, "refine_attn", probe)
     for i, spec in enumerate(refine_up):
         x = _gated(x, sd, "refine_upsample_net.%d" % i, spec)
     x = torch.clamp(x, -1., 1.)

@@ -1,5 +1,6 @@
 """Shared fixtures for the parity tests: the seeded synthetic scene of tests/golden/make_golden.py,
 rebuilt WITHOUT the reference (it does not exist on the GPU box)."""
+import functools
 import os
 
 import numpy as np
@@ -176,3 +177,146 @@ def inpaintor_state_dict(seed=1):
 def tensor_stat(x):
     x = torch.as_tensor(x).double()
     return np.array([x.mean().item(), x.abs().mean().item(), (x * x).mean().item()])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The inpaintor's self-attention on its own (lwg_inpaint_attention): case builders and the fp64 reference.
+#   out = gamma * softmax((q + b_q)(k + b_k)^T)(v + b_v) + x,  qkv (N,192) raw [q 16 | k 16 | v 128 | 32 unused], bias (192) alike
+ATTN_D, ATTN_C, ATTN_LD, ATTN_TILE = 16, 128, 192, 32
+# token count -> key chunks lwg_inpaint_create picks for the matrix-core kernel (tests/test_abi.py reads the same numbers back
+# from lwg_inpaint_attention_workspace_bytes): 1, 2, 6 and 8 tiles of 32 keys per chunk
+ATTN_PRODUCT_CHUNKS = {256: 8, 1024: 16, 2304: 12, 4096: 16}
+
+
+def _attn_pack(q, k, v, bq, bk, bv, x, gamma):
+    """Targets (q, k, v: what the kernel must see AFTER the bias add) -> the raw buffers: raw = target - bias."""
+    N = q.shape[0]
+    qkv = torch.zeros(N, ATTN_LD, dtype=torch.float32)
+    qkv[:, :ATTN_D], qkv[:, ATTN_D:2 * ATTN_D], qkv[:, 2 * ATTN_D:2 * ATTN_D + ATTN_C] = q - bq, k - bk, v - bv
+    bias = torch.zeros(ATTN_LD, dtype=torch.float32)
+    bias[:ATTN_D], bias[ATTN_D:2 * ATTN_D], bias[2 * ATTN_D:2 * ATTN_D + ATTN_C] = bq, bk, bv
+    return dict(qkv=qkv, bias=bias, x=x.float().contiguous(), gamma=float(gamma), N=N)
+
+
+def attention_onehot_case(N, winners="perm", seed=0):
+    """A softmax that is EXACTLY one-hot in fp32.  Key j is the 12-bit +-1 code of j (dimensions 12-15 zero), query i is 64 x the
+    code of perm[i]: the winning logit is 64 * 12 = 768, any other key differs in >= 1 bit, <= 640, and exp(-128) is 0 in fp32
+    (smallest denormal 1.4e-45): every other probability is exactly 0, l exactly 1.  V, x and the biases lie on a 2^-8 grid with
+    |.| <= 4, gamma = 0.5, raw = target - bias (exact, so is the kernel's bias add): every product and sum of the computation is
+    exact and the output is 0.5 * (v + b_v)[perm[i]] + x[i] bit for bit, whatever the summation order or contraction.
+    winners: 'perm' a seeded permutation; 'first' / 'last': every winner inside the first / last 32-key tile (nothing / everything
+    accumulated before it has to be rescaled by exactly 0).  -> case dict with 'expected' (N,128) and 'perm'."""
+    assert N <= 4096
+    g = torch.Generator().manual_seed(1000 + seed)
+    grid = lambda lo, hi, *shape: torch.randint(lo, hi + 1, shape, generator=g).float() / 256.0
+    code = torch.zeros(N, ATTN_D)
+    idx = torch.arange(N)
+    for b in range(12):
+        code[:, b] = ((idx >> b) & 1).float() * 2 - 1
+    if winners == "perm":
+        perm = torch.randperm(N, generator=g)
+    else:
+        perm = torch.randint(0, ATTN_TILE, (N,), generator=g) + (0 if winners == "first" else N - ATTN_TILE)
+    v, x = grid(-1024, 1024, N, ATTN_C), grid(-1024, 1024, N, ATTN_C)
+    bq, bk, bv = grid(-64, 64, ATTN_D), grid(-64, 64, ATTN_D), grid(-64, 64, ATTN_C)
+    case = _attn_pack(64.0 * code[perm], code, v, bq, bk, bv, x, 0.5)
+    case["perm"] = perm
+    case["expected"] = 0.5 * v[perm] + x
+    return case
+
+
+def attention_random_case(N, logit_std, seed=0):
+    """Raw q, k ~ N(0, s^2) with 4 s^2 = logit_std (16 products of two N(0, s^2) values), V, x ~ N(0,1), biases ~ N(0, 0.1^2),
+    gamma = 0.7.  logit_std 2 and 8 give a peaked softmax (a few to a few hundred effective keys), 0.05 the flat one of the seeded
+    network."""
+    g = torch.Generator().manual_seed(2000 + seed)
+    r = lambda *shape: torch.randn(*shape, generator=g)
+    s = (logit_std / 4.0) ** 0.5
+    qkv = torch.zeros(N, ATTN_LD)
+    qkv[:, :2 * ATTN_D] = r(N, 2 * ATTN_D) * s
+    qkv[:, 2 * ATTN_D:2 * ATTN_D + ATTN_C] = r(N, ATTN_C)
+    bias = torch.zeros(ATTN_LD)
+    bias[:2 * ATTN_D + ATTN_C] = r(2 * ATTN_D + ATTN_C) * 0.1
+    return dict(qkv=qkv, bias=bias, x=r(N, ATTN_C), gamma=0.7, N=N)
+
+
+def attention_parts(case, dtype=torch.float64):
+    """(logits (N,N), v + b_v (N,128)) of a case, the float32 inputs converted to `dtype` before the first operation."""
+    qkv, bias = case["qkv"].to(dtype), case["bias"].to(dtype)
+    t = qkv + bias
+    return t[:, :ATTN_D] @ t[:, ATTN_D:2 * ATTN_D].T, t[:, 2 * ATTN_D:2 * ATTN_D + ATTN_C]
+
+
+def attention_reference(case, dtype=torch.float64):
+    """out = gamma * softmax((q + b_q)(k + b_k)^T)(v + b_v) + x, plainly, in `dtype` (float64: the reference; float32: the yardstick
+    of what fp32 arithmetic costs on these inputs)."""
+    logits, v = attention_parts(case, dtype)
+    return case["gamma"] * (torch.softmax(logits, dim=-1) @ v) + case["x"].to(dtype)
+
+
+@functools.lru_cache(maxsize=None)
+def _attention_ref_and_yardstick(N, logit_std):
+    case = attention_random_case(N, logit_std)
+    ref = attention_reference(case)
+    return ref, float((attention_reference(case, torch.float32).double() - ref).abs().max())
+
+
+def attention_checked_case(N, logit_std):
+    """attention_random_case (a fresh dict per call) plus 'ref' (the fp64 reference) and 'yardstick' (max |fp32 evaluation - ref| of
+    the same formula on the same inputs), those two computed once per process.  The GPU kernels are fp32 with another summation
+    order and another expf: ATTN_TOL_FACTOR x the yardstick is their bound."""
+    case = attention_random_case(N, logit_std)
+    ref, case["yardstick"] = _attention_ref_and_yardstick(N, logit_std)
+    case["ref"] = ref.clone()
+    return case
+
+
+ATTN_TOL_FACTOR = 4.0
+
+
+def effective_keys(logits):
+    """1 / sum p^2 per query: how many keys share the softmax."""
+    p = torch.softmax(logits.double(), dim=-1)
+    return 1.0 / (p * p).sum(-1)
+
+
+def attention_mutant(case, which, key_chunks):
+    """The fp64 reference with one indexing bug of the kind the kernels could have:
+    'pair'    V rows of keys k and k ^ 4 swapped (the half-wave pairing of p[r] with V rows);
+    'tiles'   V tiles 0 and 1 (keys 0-31 / 32-63) swapped (a stale double buffer);
+    'chunk'   the last of key_chunks key chunks dropped, the rest renormalised (a lost partial);
+    'rescale' online softmax over 32-key tiles whose accumulator is never rescaled when the running max moves (l is)."""
+    logits, v = attention_parts(case)
+    N = case["N"]
+    idx = torch.arange(N)
+    if which == "pair":
+        attn = torch.softmax(logits, -1) @ v[idx ^ 4]
+    elif which == "tiles":
+        j = idx.clone()
+        j[:ATTN_TILE], j[ATTN_TILE:2 * ATTN_TILE] = idx[ATTN_TILE:2 * ATTN_TILE], idx[:ATTN_TILE]
+        attn = torch.softmax(logits, -1) @ v[j]
+    elif which == "chunk":
+        keep = N - N // key_chunks
+        attn = torch.softmax(logits[:, :keep], -1) @ v[:keep]
+    elif which == "rescale":
+        tmax = logits.view(N, N // ATTN_TILE, ATTN_TILE).max(-1).values
+        run = torch.cummax(tmax, dim=1).values                              # the running max when a tile is accumulated
+        m = run[:, -1:]
+        p_stale = torch.exp(logits - run.repeat_interleave(ATTN_TILE, dim=1))   # never brought down to the final max
+        attn = (p_stale @ v) / torch.exp(logits - m).sum(-1, keepdim=True)
+    else:
+        raise ValueError(which)
+    return case["gamma"] * attn + case["x"].double()
+
+
+def split_bf16_encode(r):
+    """fp32 (N, C), C % 32 == 0 -> the split-bf16 format (csrc/conv.h, split.h) as (hi, lo) bf16 tensors of r's shape."""
+    hi = r.to(torch.bfloat16)
+    return hi, (r - hi.float()).to(torch.bfloat16)
+
+
+def split_bf16_decode(buf):
+    """A split-bf16 buffer viewed as fp32 (N, C) -> (hi, lo) bf16 (N, C): per 32 channels, 128 bytes = [32 bf16 hi | 32 bf16 lo]."""
+    N, C = buf.shape
+    h = buf.contiguous().view(torch.bfloat16).view(N, C // 32, 2, 32)
+    return h[:, :, 0].reshape(N, C), h[:, :, 1].reshape(N, C)

@@ -38,6 +38,35 @@ def test_argument_validation_without_a_device():
     assert b"NULL" in lib.lwg_last_error()
     assert lib.lwg_grid_sample(None, 1, 1, 1, 1, None, 1, 1, 1, 0, None, None) == -1
     assert lib.lwg_generator_missing_weights(None) == -1
+    # lwg_inpaint_attention: every refusal comes before the first launch (the pointers below are never dereferenced)
+    ws_bytes = lib.lwg_inpaint_attention_workspace_bytes
+    for n, chunks in ((256, 8), (1024, 16), (2304, 12), (4096, 16)):   # the key chunks lwg_inpaint_create picks
+        assert ws_bytes(n, 1, 0) == chunks * n * (128 + 2) * 4 == ws_bytes(n, 1, chunks), n
+    assert ws_bytes(1024, 1, 2) == 2 * 1024 * 130 * 4
+    assert ws_bytes(1024, 0, 0) == 0 and ws_bytes(0, 1, 0) == 0 and ws_bytes(1000, 1, 0) == 0 and ws_bytes(1024, 1, 3) == 0
+    p = ctypes.c_void_p(4096)
+    big = 1 << 30
+    attn = lambda qkv, bias, x, n, kernel, chunks, split, out, ws, nbytes: lib.lwg_inpaint_attention(
+        qkv, bias, x, 0.5, n, kernel, chunks, split, out, ws, nbytes, None)
+    INVALID, UNSUPPORTED, WORKSPACE = -1, -2, -3
+    for nulled in range(4):                                       # NULL qkv / bias / x / out
+        args = [p, p, p, p]
+        args[nulled] = None
+        assert attn(args[0], args[1], args[2], 1024, 1, 0, 0, args[3], p, big) == INVALID
+        assert b"NULL" in lib.lwg_last_error()
+    assert attn(p, p, p, 1024, 1, 0, 0, p, None, 0) == INVALID        # the matrix-core kernel needs its workspace
+    assert attn(p, p, p, 0, 0, 0, 0, p, None, 0) == INVALID           # N <= 0
+    assert attn(p, p, p, -64, 1, 0, 0, p, p, big) == INVALID
+    assert attn(p, p, p, 1024, 2, 0, 0, p, p, big) == INVALID         # no such kernel
+    assert attn(p, p, p, 1024, 1, -1, 0, p, p, big) == INVALID
+    assert attn(ctypes.c_void_p(4100), p, p, 1024, 0, 0, 0, p, None, 0) == INVALID   # float4 accesses: 16-byte alignment
+    assert attn(p, p, p, 96, 0, 0, 0, p, None, 0) == UNSUPPORTED      # vector ALU: 64 queries per workgroup
+    assert attn(p, p, p, 1024, 0, 0, 1, p, None, 0) == UNSUPPORTED    # vector ALU: no split-bf16 output
+    assert attn(p, p, p, 320, 1, 0, 0, p, p, big) == UNSUPPORTED      # matrix cores: 256 queries per workgroup
+    assert attn(p, p, p, 1024, 1, 3, 0, p, p, big) == UNSUPPORTED     # 1024 keys are not 3 chunks of whole 32-key tiles
+    assert attn(p, p, p, 1024, 1, 64, 0, p, p, big) == UNSUPPORTED    # 16 keys per chunk: less than a tile
+    assert b"key chunks" in lib.lwg_last_error()
+    assert attn(p, p, p, 1024, 1, 0, 0, p, p, ws_bytes(1024, 1, 0) - 1) == WORKSPACE
 
 
 def test_product_path_fails_loudly_without_gpu():
