@@ -33,6 +33,7 @@ SOURCES = [
     ("heads.hip", []),
     ("generator.hip", []),
     ("inpaint.hip", []),
+    ("hmr.hip", ["-fno-slp-vectorize"]),
     ("train.hip", []),
     ("scatter.hip", []),
 ]

@@ -1,5 +1,6 @@
 """Builds the synthetic configuration BASELINE.json names: random-init ImpersonatorGenerator + synthetic SMPL
 (no downloaded assets).  Used by bench.py, run_imitator.py --synthetic, __graft_entry__.smoke() and the tests."""
+import os
 import types
 
 import numpy as np
@@ -68,7 +69,14 @@ def build_synthetic_imitator(batch_size=8, seed=0, image_size=256, affine="ident
     shapes = [(k, tuple(v.shape)) for k, v in gen.state_dict().items()]
     sd = synthetic.random_state_dict(shapes, seed=seed, affine=affine)
     gen.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
-    hmr = HumanModelRecovery(smpl_params=synthetic_smpl_params(seed))
+    hmr_model = getattr(opt, 'hmr_model', '')
+    if hmr_model and os.path.isfile(hmr_model):
+        # the full regressor (networks/hmr.py) over the synthetic body model: SMPLs can then be estimated from images
+        from .networks import hmr as hmr_net
+        hmr = hmr_net.load_checkpoint(hmr_net.HumanModelRecovery(smpl_params=synthetic_smpl_params(seed), max_batch=max(1, batch_size)),
+                                      hmr_model).eval()
+    else:
+        hmr = HumanModelRecovery(smpl_params=synthetic_smpl_params(seed))
     if model == "swapper":
         part_fn, part_faces = synthetic.part_map_fn(rest, faces)
         imitator = Swapper(opt, hmr=hmr, render=render, generator=gen, part_fn=part_fn, part_faces=part_faces)

@@ -77,8 +77,55 @@ class Imitator(BaseModel):
         return net
 
     def _create_hmr(self):
+        """imitator.py:69-74.  With an `--hmr_model` checkpoint on disk: the full regressor (networks/hmr.py), so that SMPLs
+        can be estimated from images; without one: the light class (`get_details` only; SMPL vectors must be passed)."""
+        opt = self._opt
+        hmr_model = getattr(opt, 'hmr_model', '')
+        if hmr_model and os.path.isfile(hmr_model):
+            from ..networks import hmr as hmr_net
+            net = NetworksFactory.get_by_name('hmr', opt.smpl_model, max_batch=max(1, int(opt.batch_size)))
+            hmr_net.load_checkpoint(net, hmr_model)
+            print('Loading net: %s' % hmr_model)
+            return net.eval()
         from ..networks.batch_smpl import HumanModelRecovery
-        return HumanModelRecovery(self._opt.smpl_model).eval()
+        return HumanModelRecovery(opt.smpl_model).eval()
+
+    def _has_regressor(self):
+        return hasattr(self.hmr, 'regressor')
+
+    def _hmr_image(self, input_file):
+        """path | HxWx3 uint8 array | (3,H,W) float array or tensor in [-1,1] -> (3,224,224) float32 host array in [-1,1]
+        (imitator.py:92,149-151: `cv_utils.transform_img(img, 224) * 2 - 1`)."""
+        img = cv_utils.read_cv2_img(input_file) if isinstance(input_file, str) else input_file
+        if torch.is_tensor(img):
+            img = img.detach().cpu().numpy()
+        img = np.asarray(img)
+        if img.dtype != np.uint8:
+            # a normalised CHW image: back to the uint8 HWC form the reference's resize works on
+            chw = img.reshape(3, img.shape[-2], img.shape[-1]).astype(np.float32)
+            if chw.shape[1] == 224 and chw.shape[2] == 224:
+                return np.ascontiguousarray(chw)
+            img = np.clip((chw.transpose(1, 2, 0) + 1.0) * 127.5, 0, 255).astype(np.uint8)
+        return np.ascontiguousarray(cv_utils.transform_img(img, 224, transpose=True) * 2 - 1.0, dtype=np.float32)
+
+    @torch.no_grad()
+    def _extract_smpls(self, input_file):
+        """imitator.py:147-155: the SMPL vector (85,) of one image, estimated by the HMR regressor."""
+        if not self._has_regressor():
+            raise NotImplementedError("estimating SMPL from an image needs the HMR regressor: give --hmr_model a checkpoint "
+                                      "(networks/hmr.py), or pass the SMPL vectors")
+        img = torch.from_numpy(self._hmr_image(input_file)).cuda()[None, ...]
+        return self.hmr(img)[-1]
+
+    @torch.no_grad()
+    def _extract_smpls_batched(self, input_files):
+        """(len, 85) device tensor: the images are loaded on the host and run through the regressor `batch_size` at a time."""
+        bs = max(1, int(self._opt.batch_size))
+        out = []
+        for s in range(0, len(input_files), bs):
+            imgs = np.stack([self._hmr_image(f) for f in input_files[s:s + bs]])
+            out.append(self.hmr(torch.from_numpy(imgs).cuda()))
+        return torch.cat(out, dim=0)
 
     def visualize(self, *args, **kwargs):
         visualizer = args[0]
@@ -106,9 +153,14 @@ class Imitator(BaseModel):
         opt = self._opt
         img, ori_img = self._load_image(src_path, opt.image_size)
         if src_smpl is None:
-            raise NotImplementedError("estimating SMPL from the image needs the HMR regressor (networks/hmr.py), "
-                                      "which is outside the Imitator.forward() path; pass src_smpl")
-        src_smpl = torch.as_tensor(np.asarray(src_smpl), dtype=torch.float32).cuda().reshape(1, -1)
+            if not self._has_regressor():
+                raise NotImplementedError("estimating SMPL from the image needs the HMR regressor (networks/hmr.py), "
+                                          "which is outside the Imitator.forward() path; pass src_smpl")
+            src_smpl = self._extract_smpls(src_path).reshape(1, -1)     # imitator.py:91-94
+        elif torch.is_tensor(src_smpl):
+            src_smpl = src_smpl.detach().float().cuda().reshape(1, -1)
+        else:
+            src_smpl = torch.as_tensor(np.asarray(src_smpl), dtype=torch.float32).cuda().reshape(1, -1)
 
         src_info = self.hmr.get_details(src_smpl)
         src_f2verts, src_fim, src_wim = self.render.render_fim_wim(src_info['cam'], src_info['verts'])
@@ -221,7 +273,9 @@ class Imitator(BaseModel):
     def transfer_params(self, tgt_path, tgt_smpl=None, cam_strategy='smooth', t=0):
         """imitator.py:270-283."""
         if tgt_smpl is None:
-            raise NotImplementedError("estimating SMPL from target images needs the HMR regressor; pass tgt_smpl")
+            if not self._has_regressor():
+                raise NotImplementedError("estimating SMPL from target images needs the HMR regressor; pass tgt_smpl")
+            tgt_smpl = self._extract_smpls(tgt_path)
         tsf_inputs = self.transfer_params_by_smpl(tgt_smpl=tgt_smpl, cam_strategy=cam_strategy, t=t)
         self.tsf_info['image'] = cv_utils.read_cv2_img(tgt_path) if isinstance(tgt_path, str) and tgt_path else None
         return tsf_inputs
@@ -472,7 +526,12 @@ class Imitator(BaseModel):
     def _run_batches(self, tgt_smpls, cam_strategy, on_batch):
         if len(tgt_smpls) == 0:      # the reference's loop over range(0) (imitator.py:166,196): nothing to do
             return []
-        smpls = torch.as_tensor(np.asarray(tgt_smpls), dtype=torch.float32).reshape(len(tgt_smpls), -1)
+        if not torch.is_tensor(tgt_smpls) and all(torch.is_tensor(t) for t in tgt_smpls):
+            tgt_smpls = torch.stack([t.reshape(-1) for t in tgt_smpls])      # a list of _extract_smpls results
+        if torch.is_tensor(tgt_smpls):
+            smpls = tgt_smpls.detach().float().reshape(len(tgt_smpls), -1)    # e.g. the regressor's output: stays on its device
+        else:
+            smpls = torch.as_tensor(np.asarray(tgt_smpls), dtype=torch.float32).reshape(len(tgt_smpls), -1)
         bs = max(1, int(self._opt.batch_size))
         outputs = []
         if cam_strategy == 'smooth' and len(smpls):
@@ -490,7 +549,9 @@ class Imitator(BaseModel):
                   verbose=True):
         """imitator.py:157-189 -> list of (H,W,3) float arrays in [-1,1]."""
         if tgt_smpls is None:
-            raise NotImplementedError("estimating SMPL from target images needs the HMR regressor; pass tgt_smpls")
+            if not self._has_regressor():
+                raise NotImplementedError("estimating SMPL from target images needs the HMR regressor; pass tgt_smpls")
+            tgt_smpls = self._extract_smpls_batched(list(tgt_paths))
 
         def sink(t, pred, pred_dev):
             if visualizer is not None:

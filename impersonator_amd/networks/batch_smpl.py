@@ -221,7 +221,9 @@ class SMPL(nn.Module):
 
 class HumanModelRecovery(nn.Module):
     """The part of networks/hmr.py on the Imitator path when target SMPL vectors are given:
-    `get_details` (hmr.py:302-330).  The image -> theta ResNet-50 regressor is out of scope (SURVEY.md section 2, #6)."""
+    `get_details` (hmr.py:302-330).  This LIGHT class holds the body model only (what the synthetic configuration and the
+    tests construct); the image -> theta ResNet-50 regressor is `networks.hmr.HumanModelRecovery`, which extends it with
+    `resnet`, `regressor` and a working `forward` (Imitator builds it when `--hmr_model` names a checkpoint)."""
 
     def __init__(self, smpl_pkl_path=None, smpl_params=None):
         super().__init__()

@@ -33,4 +33,7 @@ class NetworksFactory(object):
         if network_name == 'deepfillv2':
             from .inpaintor import InpaintSANet
             return InpaintSANet(*args, **kwargs)
+        if network_name == 'hmr':
+            from .hmr import HumanModelRecovery
+            return HumanModelRecovery(*args, **kwargs)
         raise ValueError("Network %s is not part of the MI355X Imitator.forward path" % network_name)

@@ -196,3 +196,52 @@ def random_inpaintor_state_dict(shapes, seed=0):
         else:   # conv biases, BatchNorm bias
             out[key] = (rng.standard_normal(shape, dtype=np.float32) * np.float32(0.1))
     return out
+
+
+def hmr_state_dict(seed, num_blocks=(3, 4, 6, 3)):
+    """Seeded weights of the HMR regressor (networks/hmr.py of the reference: `resnet.*` and `regressor.*`, in state_dict order;
+    the body model's `smpl.*` entries are not part of it).  numpy RandomState, one draw per tensor: He-normal conv and linear
+    weights (the last linear layer 0.1 of that, as its small-xavier initialisation), small biases, and NON-TRIVIAL BatchNorm --
+    gamma ~ U(0.5,1.5), beta ~ N(0,0.1), running_mean ~ N(0,0.2), running_var ~ U(0.5,2) -- because an identity BatchNorm would
+    let a wrong fold pass.  mean_theta = [0.9, 0, 0, pi, small ...] (scale 0.9, upright root rotation: hmr.py:198-204)."""
+    rs = np.random.RandomState(seed)
+    out = {}
+
+    def conv(key, cout, cin, k, bias):
+        out[key + ".weight"] = (rs.standard_normal((cout, cin, k, k)) * math.sqrt(2.0 / (cin * k * k))).astype(np.float32)
+        if bias:
+            out[key + ".bias"] = (rs.standard_normal(cout) * 0.05).astype(np.float32)
+
+    def bn(key, c):
+        out[key + ".weight"] = rs.uniform(0.5, 1.5, c).astype(np.float32)
+        out[key + ".bias"] = (rs.standard_normal(c) * 0.1).astype(np.float32)
+        out[key + ".running_mean"] = (rs.standard_normal(c) * 0.2).astype(np.float32)
+        out[key + ".running_var"] = rs.uniform(0.5, 2.0, c).astype(np.float32)
+        out[key + ".num_batches_tracked"] = np.zeros((), np.int64)
+
+    def linear(key, cout, cin, gain=1.0):
+        out[key + ".weight"] = (rs.standard_normal((cout, cin)) * (gain * math.sqrt(2.0 / cin))).astype(np.float32)
+        out[key + ".bias"] = (rs.standard_normal(cout) * 0.05).astype(np.float32)
+
+    conv("resnet.conv1", 64, 3, 7, True)
+    in_planes = 64
+    for li, (planes, nb) in enumerate(zip((64, 128, 256, 512), num_blocks)):
+        for bi in range(nb):
+            key = "resnet.layer%d.%d" % (li + 1, bi)
+            bn(key + ".bn1", in_planes)
+            conv(key + ".conv1", planes, in_planes, 1, False)
+            bn(key + ".bn2", planes)
+            conv(key + ".conv2", planes, planes, 3, False)
+            bn(key + ".bn3", planes)
+            conv(key + ".conv3", 4 * planes, planes, 1, True)
+            if in_planes != 4 * planes:
+                conv(key + ".shortcut.0", 4 * planes, in_planes, 1, True)
+            in_planes = 4 * planes
+    bn("resnet.post_bn", 2048)
+    mean = (rs.standard_normal(85) * 0.05).astype(np.float32)
+    mean[0:4] = (0.9, 0.0, 0.0, math.pi)
+    out["regressor.mean_theta"] = mean
+    linear("regressor.fc_blocks.fc1", 1024, 2048 + 85)
+    linear("regressor.fc_blocks.fc2", 1024, 1024)
+    linear("regressor.fc_blocks.fc3", 85, 1024, gain=0.1)
+    return out

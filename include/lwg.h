@@ -302,6 +302,52 @@ LWG_API int lwg_inpaint_attention(const float *qkv, const float *bias, const flo
                                   int key_chunks, int split_out, float *out, void *workspace, size_t workspace_bytes,
                                   lwg_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * HMR regressor: replaces what PyTorch dispatches for HumanModelRecovery.forward (networks/hmr.py:119-300) in eval mode:
+ * a pre-activation ResNet-50 (53 convolutions, BatchNorm on running statistics, max pool, average pool) and the
+ * 3-iteration ThetaRegressor.  Exact fp32 (v_mfma_f32_32x32x2_f32); NHWC activations with the pixel dimension flattened
+ * across images, so every row of a batch is bit-identical to the same image run alone, whatever max_batch is.
+ * One stream, no host synchronisation, no allocation after create: a forward can be captured in a HIP graph.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct lwg_hmr lwg_hmr;
+/* num_blocks: bottleneck blocks per layer (hmr.py:176-177), NULL = {3,4,6,3}.  Scratch for batches up to max_batch. */
+LWG_API int lwg_hmr_create(lwg_hmr **out, int max_batch, const int *num_blocks);
+LWG_API void lwg_hmr_destroy(lwg_hmr *h);
+/* The weights as ONE packed fp32 blob (HOST memory) of lwg_hmr_weight_floats() floats, everything laid out for the kernels and
+ * BatchNorm folded to scale = gamma / sqrt(var + 1e-5), shift = beta - mean * scale by the caller (in fp64, rounded once;
+ * impersonator_amd/networks/hmr.py::pack_weights is the one writer).  Order:
+ *   stem w (7,7,3,64) [kh][kw][ci][co] | stem bias (64)
+ *   per block: bn1 scale, shift (Cin) | conv1 w (Cin,p) | bn2 scale, shift (p) | conv2 w (3,3,p,p) | bn3 scale, shift (p)
+ *              | conv3 w (p,4p) | conv3 bias (4p) | when Cin != 4p: shortcut w (Cin,4p) | shortcut bias (4p)
+ *   post_bn scale, shift (2048) | mean_theta (85) | fc1 w (1024,2133), b | fc2 w (1024,1024), b | fc3 w (85,1024), b
+ * Synchronises the device (the blob is replaced under no running forward). */
+LWG_API size_t lwg_hmr_weight_floats(const lwg_hmr *h);
+LWG_API int lwg_hmr_set_weights(lwg_hmr *h, const float *blob_host, size_t n_floats);
+/* images (n,3,height,width) NCHW in [-1,1], height = width = 224 (anything else: LWG_ERR_UNSUPPORTED), n <= max_batch
+ * -> theta_out (n,85) = [cam 3 | pose 72 | shape 10]; features_out (n,2048) or NULL. */
+LWG_API int lwg_hmr_forward(lwg_hmr *h, const float *images, int n, int height, int width, float *theta_out,
+                            float *features_out, lwg_stream_t stream);
+/* Op-level entry points (what lwg_hmr_forward is made of; the tests call them directly).
+ * conv: x (N,H,W,Cin) NHWC, w (k,k,Cin,Cout) [kh][kw][ci][co] -> y (N,Ho,Wo,Cout); (k,stride,pad) one of (1,1,0) (3,1,1) (3,2,1)
+ *   (7,2,3); Cout a multiple of 64; any N, H, W >= 1.  All optional (NULL): prologue x <- max(x*pre_scale[ci] + pre_shift[ci], 0) on
+ *   the input (padding stays 0); epilogue v + bias[co], then max(v*post_scale[co] + post_shift[co], 0), then + residual[n, oh*res_stride,
+ *   ow*res_stride, co] of an NHWC tensor (N,res_H,res_W,Cout).  Pointers 16-byte aligned.
+ * maxpool: F.max_pool2d(kernel 3, stride 2, ceil_mode=True), no padding: (N,H,W,C) -> (N,ceil((H-3)/2)+1,ceil((W-3)/2)+1,C); C % 4 == 0.
+ * pool_features: out (N,C) = mean over the HW pixels of max(x*scale + shift, 0); x (N,HW,C).
+ * regress: ThetaRegressor.forward (hmr.py:239-252): features (N,2048), weights in PyTorch layout on the DEVICE -> theta_out (N,85);
+ *   workspace: lwg_hmr_regress_workspace_bytes(N), scratch only. */
+LWG_API int lwg_hmr_conv(const float *x, int N, int H, int W, int Cin, const float *w, int Cout, int k, int stride, int pad,
+                         const float *pre_scale, const float *pre_shift, const float *bias, const float *post_scale,
+                         const float *post_shift, const float *residual, int res_stride, int res_H, int res_W, float *y,
+                         lwg_stream_t stream);
+LWG_API int lwg_hmr_maxpool(const float *x, int N, int H, int W, int C, float *y, lwg_stream_t stream);
+LWG_API int lwg_hmr_pool_features(const float *x, int N, int HW, int C, const float *scale, const float *shift, float *out,
+                                  lwg_stream_t stream);
+LWG_API size_t lwg_hmr_regress_workspace_bytes(int N);
+LWG_API int lwg_hmr_regress(const float *features, int N, const float *mean_theta, const float *fc1_w, const float *fc1_b,
+                            const float *fc2_w, const float *fc2_b, const float *fc3_w, const float *fc3_b, float *theta_out,
+                            void *workspace, size_t workspace_bytes, lwg_stream_t stream);
+
 /* ---- training, first slice: the PatchGAN discriminator update ---------------------------------
  * Replaces PatchDiscriminator.forward (networks/discriminator.py:8-57, norm_type='instance', use_sigmoid=False) and,
  * for the discriminator, ImpersonatorTrainer._optimize_D + loss.backward() + torch.optim.Adam.step()

@@ -5,8 +5,12 @@
     python run_imitator.py --synthetic --num_frames 64 --output_dir OUT                          (no assets)
     python -m torch.distributed.run --nproc-per-node 8 ... run_imitator.py --synthetic ...       (8 GPUs, frame-sharded)
 
-With real assets the SMPL parameters of source and targets must be supplied as `<image>.smpl.npy` files next to the
-images (the HMR image regressor that the reference uses to estimate them is outside this build's scope).
+    python run_imitator.py --synthetic --hmr_model H.pth --src_path S.jpg --tgt_path DIR --output_dir OUT
+                                                      (synthetic body model and generator, SMPLs estimated from the images)
+
+When `--hmr_model` names a checkpoint of the HMR regressor (the reference's hmr_tf2pt.pth, or one saved from
+`utils.synthetic.hmr_state_dict`), the SMPL parameters of source and targets are estimated from the images as the reference
+does.  An `<image>.smpl.npy` file next to an image takes precedence; without a regressor those files are required.
 """
 import glob
 import os
@@ -33,11 +37,22 @@ def scan_tgt_paths(tgt_path, itv=20):
     return paths
 
 
-def _smpl_of(path):
+def _smpl_of(path, optional=False):
     f = path + '.smpl.npy'
     if not os.path.exists(f):
-        raise FileNotFoundError("%s: SMPL vector (85,) expected next to the image" % f)
+        if optional:
+            return None
+        raise FileNotFoundError("%s: SMPL vector (85,) expected next to the image (or give --hmr_model a checkpoint)" % f)
     return np.load(f).astype(np.float32).reshape(85)
+
+
+def _target_smpls(imitator, tgt_paths):
+    """(len, 85): the `.smpl.npy` files where every target has one, else the regressor's estimates."""
+    have_hmr = hasattr(imitator.hmr, 'regressor')
+    given = [_smpl_of(p, optional=have_hmr) for p in tgt_paths]
+    if all(g is not None for g in given):
+        return np.stack(given)
+    return imitator._extract_smpls_batched(tgt_paths).cpu().numpy()
 
 
 def main():
@@ -51,10 +66,16 @@ def main():
             batch_size=opt.batch_size, image_size=opt.image_size,
             opt=demo.default_opt(batch_size=opt.batch_size, image_size=opt.image_size, front_warp=opt.front_warp,
                                  only_vis=opt.only_vis, align_corners=opt.align_corners,
-                                 map_name=getattr(opt, 'map_name', 'uv_seg')))
-        imitator.personalize(src_img, src_smpl=src_smpl, bg_img=bg_img)
-        tgt_smpls = demo.synthetic_smpls(opt.num_frames, seed=0)
-        tgt_paths = None
+                                 map_name=getattr(opt, 'map_name', 'uv_seg'), hmr_model=opt.hmr_model))
+        if hasattr(imitator.hmr, 'regressor') and opt.src_path:
+            # pictures in, pictures out: SMPLs of the source and of the targets come from the HMR regressor
+            imitator.personalize(opt.src_path, bg_img=bg_img)
+            tgt_paths = scan_tgt_paths(opt.tgt_path, itv=1) if opt.tgt_path else None
+            tgt_smpls = _target_smpls(imitator, tgt_paths) if tgt_paths else demo.synthetic_smpls(opt.num_frames, seed=0)
+        else:
+            imitator.personalize(src_img, src_smpl=src_smpl, bg_img=bg_img)
+            tgt_smpls = demo.synthetic_smpls(opt.num_frames, seed=0)
+            tgt_paths = None
     else:
         from impersonator_amd.models.imitator import Imitator
         imitator = Imitator(opt)
@@ -62,9 +83,10 @@ def main():
         bg_file = opt.src_path + '.bg.npy'
         if os.path.exists(bg_file):
             bg = np.load(bg_file)
-        imitator.personalize(opt.src_path, src_smpl=_smpl_of(opt.src_path), bg_img=bg)
+        have_hmr = hasattr(imitator.hmr, 'regressor')
+        imitator.personalize(opt.src_path, src_smpl=_smpl_of(opt.src_path, optional=have_hmr), bg_img=bg)
         tgt_paths = scan_tgt_paths(opt.tgt_path, itv=1)
-        tgt_smpls = np.stack([_smpl_of(p) for p in tgt_paths])
+        tgt_smpls = _target_smpls(imitator, tgt_paths)
 
     # frame sharding: every rank imitates its own blocks of `batch_size` frames (first_cam = frame 0's camera everywhere)
     outs = sharding.imitate_sharded(imitator, tgt_smpls, opt.batch_size, opt.cam_strategy, rank, world)
