@@ -38,6 +38,8 @@ _PROTOS = {
     "lwg_cal_bc_transform": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "lwg_grid_sample": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
     "lwg_resize_flow": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "lwg_crop_resize": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "lwg_crop_resize_backward": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "lwg_transfer_workspace_bytes": (_sz, [_i, _i, _i]),
     "lwg_transfer_frame": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp,
                                 _vp, _vp, _vp, _vp, _sz, _vp]),
@@ -96,6 +98,8 @@ _PROTOS = {
     "lwg_heads_forward": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _c.c_size_t, _vp]),
     "lwg_heads_backward_weight": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _c.c_size_t, _vp]),
     "lwg_discriminator_input_grad": (_i, [_vp, _vp, _i, _c.c_float, _vp, _vp, _vp]),
+    "lwg_discriminator_backward_scaled": (_i, [_vp, _vp, _vp, _i, _c.c_float, _vp, _vp]),
+    "lwg_discriminator_input_grad_scaled": (_i, [_vp, _vp, _i, _c.c_float, _c.c_float, _vp, _vp, _vp]),
     "lwg_grid_sample_nhwc": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
     "lwg_instance_norm_scratch_bytes": (_c.c_size_t, [_i, _i, _i]),
     "lwg_instance_norm_forward": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),

@@ -26,6 +26,7 @@ SOURCES = [
     # that may run underneath the generators altogether).  Same values: packing does not change the arithmetic.
     ("raster.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     ("warp.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
+    ("crop.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     ("smpl.hip", ["-fno-slp-vectorize"]),
     ("personalize.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     ("conv.hip", []),

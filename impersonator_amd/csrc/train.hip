@@ -85,9 +85,11 @@ __global__ __launch_bounds__(256) void d_act_kernel(const float *__restrict__ ra
 // ---- LSGAN loss and its gradient on the 1-channel patch map (channel 0 of a Cp-channel NHWC tensor).
 // Images [0, N) are real (target +1), [N, 2N) fake (target -1).  One workgroup; fixed-order reduction.
 // halves = 2: images [0,N) target t0, [N,2N) target t1, loss = mean over each half, summed; halves = 1: N images, target t0
+// scale: factor on the loss and its gradient, applied last (1.f leaves every bit as it was; the global-local discriminator's
+// branches each carry 0.5 of one mean over both patch maps)
 __global__ __launch_bounds__(256) void lsgan_kernel(const float *__restrict__ out, int N, int HW, int Cp,
                                                     float *__restrict__ dout, float *__restrict__ loss, int halves, float t0,
-                                                    float t1)
+                                                    float t1, float scale)
 {
     __shared__ double sh[256];
     const int per_half = N * HW;
@@ -97,7 +99,7 @@ __global__ __launch_bounds__(256) void lsgan_kernel(const float *__restrict__ ou
         const float d = out[(size_t)i * Cp] - y;
         acc += (double)d * d;
         float *g = dout + (size_t)i * Cp;
-        g[0] = 2.f * d / (float)per_half;
+        g[0] = (2.f * d / (float)per_half) * scale;
         for (int c = 1; c < Cp; ++c) g[c] = 0.f;
     }
     sh[threadIdx.x] = acc;
@@ -106,7 +108,7 @@ __global__ __launch_bounds__(256) void lsgan_kernel(const float *__restrict__ ou
         if (threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
         __syncthreads();
     }
-    if (threadIdx.x == 0) loss[0] = (float)(sh[0] / per_half);
+    if (threadIdx.x == 0) loss[0] = (float)(sh[0] / per_half * (double)scale);
 }
 
 // ---- backward of [InstanceNorm] + LeakyReLU.  g = dy * leaky'(y);  with norm:
@@ -2106,6 +2108,12 @@ int lwg_discriminator_forward(lwg_discriminator *d, const float *x_nchw, int bs,
 int lwg_discriminator_backward(lwg_discriminator *d, const float *real_nchw, const float *fake_nchw, int bs, float *loss_device,
                                lwg_stream_t stream)
 {
+    return lwg_discriminator_backward_scaled(d, real_nchw, fake_nchw, bs, 1.f, loss_device, stream);
+}
+
+int lwg_discriminator_backward_scaled(lwg_discriminator *d, const float *real_nchw, const float *fake_nchw, int bs, float loss_scale,
+                                      float *loss_device, lwg_stream_t stream)
+{
     int rc = d_check(d, bs);
     if (rc != LWG_OK) return rc;
     LWG_REQUIRE(real_nchw && fake_nchw, "discriminator backward: NULL argument");
@@ -2115,7 +2123,7 @@ int lwg_discriminator_backward(lwg_discriminator *d, const float *real_nchw, con
     const int B = 2 * bs, nl = (int)d->L.size();
     {
         DLayer &L = d->L[nl - 1];
-        lsgan_kernel<<<1, 256, 0, st>>>(L.raw, bs, L.Ho * L.Ho, L.cout_pad, L.dact, d->loss, 2, 1.f, -1.f);
+        lsgan_kernel<<<1, 256, 0, st>>>(L.raw, bs, L.Ho * L.Ho, L.cout_pad, L.dact, d->loss, 2, 1.f, -1.f, loss_scale);
         LWG_LAUNCH_CHECK("lsgan_kernel");
         if (loss_device) LWG_HIP(hipMemcpyAsync(loss_device, d->loss, sizeof(float), hipMemcpyDeviceToDevice, st));
     }
@@ -2824,6 +2832,13 @@ int lwg_adam_update_device_step(float *param, const float *grad, float *exp_avg,
 int lwg_discriminator_input_grad(lwg_discriminator *d, const float *x_nchw, int bs, float target, float *loss_device,
                                  float *dx_nchw, lwg_stream_t stream)
 {
+    return lwg_discriminator_input_grad_scaled(d, x_nchw, bs, target, 1.f, loss_device, dx_nchw, stream);
+}
+
+/* the same with loss = loss_scale * mean((D(x) - target)^2): the scale enters at the loss gradient, nothing is rescaled afterwards */
+int lwg_discriminator_input_grad_scaled(lwg_discriminator *d, const float *x_nchw, int bs, float target, float loss_scale,
+                                        float *loss_device, float *dx_nchw, lwg_stream_t stream)
+{
     int rc = d_check(d, bs);
     if (rc != LWG_OK) return rc;
     LWG_REQUIRE(x_nchw && dx_nchw, "discriminator input_grad: NULL argument");
@@ -2838,7 +2853,7 @@ int lwg_discriminator_input_grad(lwg_discriminator *d, const float *x_nchw, int 
     const int nl = (int)d->L.size();
     {
         DLayer &L = d->L[nl - 1];
-        lsgan_kernel<<<1, 256, 0, st>>>(L.raw, bs, L.Ho * L.Ho, L.cout_pad, L.dact, d->loss, 1, target, 0.f);
+        lsgan_kernel<<<1, 256, 0, st>>>(L.raw, bs, L.Ho * L.Ho, L.cout_pad, L.dact, d->loss, 1, target, 0.f, loss_scale);
         LWG_LAUNCH_CHECK("lsgan_kernel");
         if (loss_device) LWG_HIP(hipMemcpyAsync(loss_device, d->loss, sizeof(float), hipMemcpyDeviceToDevice, st));
     }

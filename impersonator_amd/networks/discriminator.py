@@ -6,13 +6,16 @@ models/impersonator_trainer.py:219-222: norm_type='instance', n_layers=4, use_si
 `loss.backward()`, `torch.optim.Adam.step()` (:231-232) -- into `optimize_D`.  The nn modules below only hold the
 parameters; forward, backward and Adam run in train.hip on flat device buffers.  In a data-parallel job the gradient
 buffer is all-reduced with torch.distributed (RCCL on GPUs) between backward and the Adam step: the one collective of
-the training path."""
+the training path.
+
+`GlobalLocalDiscriminator` (networks/discriminator.py:60-96, the augmented trainer's discriminator) is two of these plus the
+device body crop of ops.crop_resize."""
 import ctypes
 
 import torch
 import torch.nn as nn
 
-from .. import _lib, sharding
+from .. import _lib, ops, sharding
 from .networks import NetworkBase
 
 
@@ -112,6 +115,11 @@ class PatchDiscriminator(NetworkBase):
         dev = torch.device("cuda", torch.cuda.current_device())
         return (torch.as_tensor(_DeviceView(p.value, n.value), device=dev), torch.as_tensor(_DeviceView(g.value, n.value), device=dev))
 
+    def use_device_step(self, on=True, betas=(0.5, 0.999)):
+        """Keep Adam's step count on the device (include/lwg.h, lwg_discriminator_use_device_step): what a captured graph of
+        optimize_D needs to replay correctly.  Synchronous; call it outside a capture, with the betas the steps will use."""
+        _lib.check(_lib.load().lwg_discriminator_use_device_step(self._ensure_handle(), 1 if on else 0, float(betas[0]), float(betas[1])))
+
     def release(self):
         if self._handle is not None:
             _lib.load().lwg_discriminator_destroy(self._handle)
@@ -145,9 +153,9 @@ class PatchDiscriminator(NetworkBase):
         return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
 
     @torch.no_grad()
-    def input_grad(self, x, target=0.0):
+    def input_grad(self, x, target=0.0, loss_scale=1.0):
         """The generator's adversarial term (impersonator_trainer.py:369-371): (loss, d loss / d x) for
-        loss = mean((D(x) - target)^2); the discriminator's own parameters get no gradient."""
+        loss = loss_scale * mean((D(x) - target)^2); the discriminator's own parameters get no gradient."""
         if not x.is_cuda:
             raise RuntimeError("PatchDiscriminator runs on the MI355X only (no CPU fallback)")
         h = self._ensure_handle()
@@ -156,15 +164,19 @@ class PatchDiscriminator(NetworkBase):
             raise ValueError("expected (<=%d, %d, %d, %d) input" % (self.max_batch, self.input_nc, self.image_size, self.image_size))
         loss = torch.empty((), device=x.device, dtype=torch.float32)
         dx = torch.empty_like(x)
-        _lib.check(_lib.load().lwg_discriminator_input_grad(h, _lib.ptr(x), x.shape[0], float(target), _lib.ptr(loss), _lib.ptr(dx),
-                                                            _lib.stream_ptr()))
+        if loss_scale == 1.0:
+            _lib.check(_lib.load().lwg_discriminator_input_grad(h, _lib.ptr(x), x.shape[0], float(target), _lib.ptr(loss), _lib.ptr(dx),
+                                                                _lib.stream_ptr()))
+        else:
+            _lib.check(_lib.load().lwg_discriminator_input_grad_scaled(h, _lib.ptr(x), x.shape[0], float(target), float(loss_scale),
+                                                                       _lib.ptr(loss), _lib.ptr(dx), _lib.stream_ptr()))
         return loss, dx
 
     @torch.no_grad()
-    def optimize_D(self, real_input_D, fake_input_D, lr=0.0002, betas=(0.5, 0.999), eps=1e-8, all_reduce=True):
+    def optimize_D(self, real_input_D, fake_input_D, lr=0.0002, betas=(0.5, 0.999), eps=1e-8, all_reduce=True, loss_scale=1.0):
         """One discriminator update, impersonator_trainer.py:396-411 + backward + Adam (:231-232, train_options.py:36-38):
-        loss = mean((D(real) - 1)^2) + mean((D(fake) + 1)^2).  Returns the loss (0-d CUDA tensor, before the update).
-        With torch.distributed initialised and world_size > 1 the gradients are averaged over the ranks first."""
+        loss = loss_scale * (mean((D(real) - 1)^2) + mean((D(fake) + 1)^2)).  Returns the loss (0-d CUDA tensor, before the
+        update).  With torch.distributed initialised and world_size > 1 the gradients are averaged over the ranks first."""
         if not (real_input_D.is_cuda and fake_input_D.is_cuda):
             raise RuntimeError("PatchDiscriminator runs on the MI355X only (no CPU fallback)")
         h = self._ensure_handle()
@@ -175,8 +187,100 @@ class PatchDiscriminator(NetworkBase):
             raise ValueError("real/fake must both be (bs, %d, %d, %d)" % (self.input_nc, self.image_size, self.image_size))
         lib = _lib.load()
         loss = torch.empty((), device=real.device, dtype=torch.float32)
-        _lib.check(lib.lwg_discriminator_backward(h, _lib.ptr(real), _lib.ptr(fake), bs, _lib.ptr(loss), _lib.stream_ptr()))
+        if loss_scale == 1.0:
+            _lib.check(lib.lwg_discriminator_backward(h, _lib.ptr(real), _lib.ptr(fake), bs, _lib.ptr(loss), _lib.stream_ptr()))
+        else:
+            _lib.check(lib.lwg_discriminator_backward_scaled(h, _lib.ptr(real), _lib.ptr(fake), bs, float(loss_scale), _lib.ptr(loss),
+                                                             _lib.stream_ptr()))
         if all_reduce and sharding.collectives_active():
             sharding.average_gradients(self.flat_buffers()[1])
         _lib.check(lib.lwg_discriminator_adam_step(h, float(lr), float(betas[0]), float(betas[1]), float(eps), _lib.stream_ptr()))
         return loss
+
+
+class GlobalLocalDiscriminator(NetworkBase):
+    """networks/discriminator.py:60-96 of the reference, as the augmented trainer builds it (impersonator_trainer_aug.py:220-222):
+    a PatchGAN on the inpainted background (4 channels) and one on the synthesised person, cropped to the body box and resampled
+    to full size (ops.crop_resize: boxes read on the device).  The reference takes one mean over the concatenation of the two
+    patch maps (impersonator_trainer_aug.py:380-381, 412-425); both have one shape, so each branch runs its own handle with a
+    loss scale of 0.5 (include/lwg.h, lwg_discriminator_backward_scaled) and the two losses add up to the reference's."""
+
+    def __init__(self, input_nc, ndf=64, n_layers=3, norm_type='batch', use_sigmoid=False, image_size=256, max_batch=8,
+                 conv_precision='fp32'):
+        super().__init__()
+        self._name = 'global_local'
+        kw = dict(ndf=ndf, n_layers=n_layers, norm_type=norm_type, use_sigmoid=use_sigmoid, image_size=image_size,
+                  max_batch=max_batch, conv_precision=conv_precision)
+        self.global_model = PatchDiscriminator(4, **kw)
+        self.local_model = PatchDiscriminator(input_nc, **kw)
+        self.input_nc, self.image_size, self.max_batch, self.conv_precision = input_nc, image_size, max_batch, conv_precision
+
+    def _branches(self):
+        return (self.global_model, self.local_model)
+
+    # ---- forwarded to both branches
+    def push_parameters(self):
+        for m in self._branches():
+            m.push_parameters()
+
+    def pull_parameters(self):
+        for m in self._branches():
+            m.pull_parameters()
+
+    def gradients(self):
+        """Last backward's gradients under the state_dict's keys ('global_model.model.0.weight', ...)."""
+        return {"%s.%s" % (name, k): v for name, m in (("global_model", self.global_model), ("local_model", self.local_model))
+                for k, v in m.gradients().items()}
+
+    def flat_buffers(self):
+        """((params, grads) of the global branch, (params, grads) of the local branch)."""
+        return tuple(m.flat_buffers() for m in self._branches())
+
+    def use_device_step(self, on=True, betas=(0.5, 0.999)):
+        for m in self._branches():
+            m.use_device_step(on, betas)
+
+    def release(self):
+        for m in self._branches():
+            m.release()
+
+    def _boxes(self, local_rects, x):
+        return ops.crop_boxes(local_rects, x.shape[0], self.image_size, x.device)
+
+    @staticmethod
+    def _image(x):
+        if not x.is_cuda:
+            raise RuntimeError("GlobalLocalDiscriminator runs on the MI355X only (no CPU fallback)")
+        return x.detach().float().contiguous()
+
+    # ---- the reference's surface
+    @torch.no_grad()
+    def forward(self, global_x, local_x, local_rects):
+        """discriminator.py:70-77: cat([global_model(global_x), local_model(crop_body(local_x, local_rects))], dim=0)."""
+        local_x = self._image(local_x)
+        crop = ops.crop_resize(local_x, self._boxes(local_rects, local_x))
+        return torch.cat([self.global_model(global_x), self.local_model(crop)], dim=0)
+
+    @torch.no_grad()
+    def input_grad(self, global_x, local_x, local_rects, target=0.0):
+        """The generator's adversarial term (impersonator_trainer_aug.py:378-381): loss = mean((D(global, local, rects) - target)^2)
+        over both patch maps -> (loss, d loss / d global_x, d loss / d local_x); the latter goes back through the crop's adjoint
+        (zero outside each box).  The discriminator's parameters get no gradient."""
+        local_x = self._image(local_x)
+        boxes = self._boxes(local_rects, local_x)
+        loss_g, d_global = self.global_model.input_grad(global_x, target, loss_scale=0.5)
+        loss_l, d_crop = self.local_model.input_grad(ops.crop_resize(local_x, boxes), target, loss_scale=0.5)
+        return loss_g + loss_l, d_global, ops.crop_resize_backward(d_crop, boxes)
+
+    @torch.no_grad()
+    def optimize_D(self, real_global, real_local, fake_global, fake_local, local_rects, lr=0.0002, betas=(0.5, 0.999), eps=1e-8,
+                   all_reduce=True):
+        """One update of both branches, impersonator_trainer_aug.py:368-373, 405-422 + backward + Adam:
+        loss = mean((D(real) - 1)^2) + mean((D(fake) + 1)^2), each mean over the concatenated patch maps.  Returns the loss (0-d
+        CUDA tensor, before the update).  Gradient averaging across ranks as PatchDiscriminator.optimize_D, on both buffers."""
+        real_local, fake_local = self._image(real_local), self._image(fake_local)
+        boxes = self._boxes(local_rects, real_local)
+        loss_g = self.global_model.optimize_D(real_global, fake_global, lr, betas, eps, all_reduce, loss_scale=0.5)
+        loss_l = self.local_model.optimize_D(ops.crop_resize(real_local, boxes), ops.crop_resize(fake_local, boxes), lr, betas, eps,
+                                             all_reduce, loss_scale=0.5)
+        return loss_g + loss_l

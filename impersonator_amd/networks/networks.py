@@ -23,7 +23,7 @@ class NetworkBase(nn.Module):
 
 
 class NetworksFactory(object):
-    """networks/networks.py:9-43, restricted to the networks on the Imitator.forward path."""
+    """networks/networks.py:9-43, restricted to the networks on the Imitator.forward path and the trainers' discriminators."""
 
     @staticmethod
     def get_by_name(network_name, *args, **kwargs):
@@ -36,4 +36,10 @@ class NetworksFactory(object):
         if network_name == 'hmr':
             from .hmr import HumanModelRecovery
             return HumanModelRecovery(*args, **kwargs)
-        raise ValueError("Network %s is not part of the MI355X Imitator.forward path" % network_name)
+        if network_name == 'discriminator_patch_gan':
+            from .discriminator import PatchDiscriminator
+            return PatchDiscriminator(*args, **kwargs)
+        if network_name == 'global_local':
+            from .discriminator import GlobalLocalDiscriminator
+            return GlobalLocalDiscriminator(*args, **kwargs)
+        raise ValueError("Network %s is not part of the MI355X Imitator.forward path or its trainers" % network_name)

@@ -237,3 +237,54 @@ def grid_sample_nhwc(x, grid, align_corners=False):
     _lib.check(_lib.load().lwg_grid_sample_nhwc(_lib.ptr(x), xn, c, h, w, _lib.ptr(grid), n, ho, wo, int(align_corners), _lib.ptr(y),
                                                 _lib.stream_ptr()))
     return y
+
+
+def crop_boxes(boxes, n, size, device):
+    """The (n,4) int64 device tensor lwg_crop_resize reads, rows (min_x, max_x, min_y, max_y) with exclusive ends.  A CUDA tensor
+    goes through untouched (nothing is read back: the call stays asynchronous and capturable; the kernel clamps to the image).
+    A CPU tensor or a list is validated here -- shape (n,4), integers, 0 <= min <= max <= size -- and then copied over."""
+    if torch.is_tensor(boxes) and boxes.is_cuda:
+        if tuple(boxes.shape) != (n, 4) or boxes.dtype != torch.int64 or not boxes.is_contiguous():
+            raise ValueError("boxes on the device must be a contiguous int64 tensor of shape (%d, 4)" % n)
+        return boxes
+    b = boxes if torch.is_tensor(boxes) else torch.as_tensor(boxes)
+    if tuple(b.shape) != (n, 4):
+        raise ValueError("boxes must have shape (%d, 4), got %s" % (n, tuple(b.shape)))
+    if b.dtype.is_floating_point or b.dtype.is_complex or b.dtype == torch.bool:
+        raise ValueError("boxes must be integers, got %s" % b.dtype)
+    b = b.to(torch.int64)
+    lo, hi = b[:, 0::2], b[:, 1::2]
+    if bool((lo < 0).any()) or bool((hi > size).any()) or bool((lo > hi).any()):
+        raise ValueError("boxes must satisfy 0 <= min <= max <= %d per axis (min_x, max_x, min_y, max_y), got %s"
+                         % (size, b.tolist()))
+    return b.contiguous().to(device)
+
+
+def _crop_args(x, boxes):
+    if x.dim() != 4 or x.shape[2] != x.shape[3]:
+        raise ValueError("crop_resize takes square (n,C,S,S) NCHW images, got %s" % (tuple(x.shape),))
+    if not (torch.is_tensor(boxes) and boxes.is_cuda):
+        crop_boxes(boxes, x.shape[0], x.shape[2], "cpu")   # a bad box is refused before anything touches the device
+    _chk(x)
+    return crop_boxes(boxes, x.shape[0], x.shape[2], x.device)
+
+
+@torch.no_grad()
+def crop_resize(x, boxes):
+    """GlobalLocalDiscriminator.crop_body (networks/discriminator.py:80-96): x (n,C,S,S) NCHW, boxes (n,4) -> each sample's box
+    resampled to (S,S), bilinear with align_corners=True.  An empty box gives zeros (include/lwg.h, lwg_crop_resize)."""
+    b = _crop_args(x, boxes)
+    out = torch.empty_like(x)
+    _lib.check(_lib.load().lwg_crop_resize(_lib.ptr(x), x.shape[0], x.shape[1], x.shape[2], _lib.ptr(b), _lib.ptr(out),
+                                           _lib.stream_ptr()))
+    return out
+
+
+@torch.no_grad()
+def crop_resize_backward(dy, boxes):
+    """The adjoint of crop_resize: dy (n,C,S,S) -> dx (n,C,S,S), zero outside each box; deterministic (no atomics)."""
+    b = _crop_args(dy, boxes)
+    dx = torch.empty_like(dy)
+    _lib.check(_lib.load().lwg_crop_resize_backward(_lib.ptr(dy), dy.shape[0], dy.shape[1], dy.shape[2], _lib.ptr(b), _lib.ptr(dx),
+                                                    _lib.stream_ptr()))
+    return dx

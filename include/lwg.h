@@ -91,6 +91,21 @@ LWG_API int lwg_grid_sample(const float *x, int xn, int C, int H, int W, const f
  * of the flow field T (bs,H,W,2) -> (bs,h,w,2). */
 LWG_API int lwg_resize_flow(const float *T, int bs, int H, int W, int h, int w, float *out, lwg_stream_t stream);
 
+/* GlobalLocalDiscriminator.crop_body (networks/discriminator.py:80-96): out[i] = F.interpolate(x[i, :, min_y:max_y, min_x:max_x],
+ * size=(S,S), mode='bilinear', align_corners=True).  x, out (n,C,S,S) NCHW (the layout lwg_discriminator_forward takes);
+ * boxes (n,4) int64 IN DEVICE MEMORY, (min_x, max_x, min_y, max_y) with exclusive ends -- what cal_body_bbox / cal_head_bbox
+ * (models/impersonator_trainer_aug.py:86-166) return.  The kernel reads the boxes itself: no host read, no synchronisation,
+ * no allocation, so a captured graph replays with whatever boxes the tensor then holds.  Every coordinate is clamped to [0,S]
+ * before use; a sample whose clamped box is empty (max <= min on either axis) gets zeros.  PyTorch's align-corners arithmetic
+ * per axis: scale = (in-1)/(S-1) (0 for in == 1), src = scale*dst, i0 = floor(src), lambda = src - i0, i1 = i0 + (i0 < in-1).
+ * S <= 1024, n*C <= 65535. */
+LWG_API int lwg_crop_resize(const float *x, int n, int C, int S, const int64_t *boxes, float *out, lwg_stream_t stream);
+/* Its exact adjoint (what autograd does behind crop_body under loss.backward(), impersonator_trainer_aug.py:365): dy (n,C,S,S)
+ * -> dx (n,C,S,S), WRITTEN (not accumulated), 0.0 outside each box.  A column gather followed by a row gather in a fixed order,
+ * no atomics: bit-reproducible from run to run. */
+LWG_API int lwg_crop_resize_backward(const float *dy, int n, int C, int S, const int64_t *boxes, float *dx,
+                                     lwg_stream_t stream);
+
 /* One launch sequence for models/imitator.py:250-260 given posed vertices:
  * project -> rasterise -> cond = map_fn[fim] -> T -> tsf_img = grid_sample(src_img, T)
  * -> tsf_inputs = cat(tsf_img, cond).  Shared source: src_p2verts (nf,3,2), src_img (3,is,is).
@@ -424,6 +439,15 @@ LWG_API int lwg_heads_backward_weight(const float *x, const float *dy8, int N, i
  * x (bs,input_nc,is,is) NCHW and its gradient wrt x (same shape); the discriminator's parameters get no gradient. */
 LWG_API int lwg_discriminator_input_grad(lwg_discriminator *d, const float *x_nchw, int bs, float target, float *loss_device,
                                          float *dx_nchw, lwg_stream_t stream);
+/* lwg_discriminator_backward and lwg_discriminator_input_grad with a factor on the loss: loss = loss_scale * (...), gradients
+ * scaled with it at their source (the loss gradient on the patch map), nothing rescaled afterwards.  loss_scale = 1 gives the
+ * unscaled entry points' bits.
+ * GlobalLocalDiscriminator takes one mean over the concatenation of its two branches' patch maps (networks/discriminator.py:77,
+ * models/impersonator_trainer_aug.py:380-381, 412-425); both maps have one shape, so each branch runs with loss_scale = 0.5. */
+LWG_API int lwg_discriminator_backward_scaled(lwg_discriminator *d, const float *real_nchw, const float *fake_nchw, int bs,
+                                              float loss_scale, float *loss_device, lwg_stream_t stream);
+LWG_API int lwg_discriminator_input_grad_scaled(lwg_discriminator *d, const float *x_nchw, int bs, float target,
+                                                float loss_scale, float *loss_device, float *dx_nchw, lwg_stream_t stream);
 /* bilinear grid_sample (zeros padding) on NHWC tensors: x (xn,H,W,C), xn in {1, n}; grid (n,Ho,Wo,2) -> y (n,Ho,Wo,C) */
 LWG_API int lwg_grid_sample_nhwc(const float *x, int xn, int C, int H, int W, const float *grid, int n, int Ho, int Wo,
                                  int align_corners, float *y, lwg_stream_t stream);
