@@ -273,13 +273,33 @@ __global__ void smpl_j2d_kernel(const float *__restrict__ j3d, const float *__re
 // Viewer.rotate_trans (models/viewer.py:240-247): out = X @ R + t for every vertex, R row-major (3,3).  The rotation and the
 // translation travel as kernel arguments (a dozen floats: no upload, nothing for a graph replay to re-read from the host).
 struct RigidArgs { float R[9]; float t[3]; };
+// coordinate j of (x0,x1,x2) @ R + t: the ONE expression both rigid kernels evaluate (same operations, same order, same bits)
+__device__ __forceinline__ float rigid_coord(float x0, float x1, float x2, const float *R, const float *t, int j)
+{
+    return fmaf(x2, R[6 + j], fmaf(x1, R[3 + j], x0 * R[j])) + t[j];
+}
+
 __global__ void rotate_translate_kernel(const float *__restrict__ x, long n, RigidArgs a, float *__restrict__ out)
 {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float x0 = x[3 * i], x1 = x[3 * i + 1], x2 = x[3 * i + 2];
 #pragma unroll
-    for (int j = 0; j < 3; ++j) out[3 * i + j] = fmaf(x2, a.R[6 + j], fmaf(x1, a.R[3 + j], x0 * a.R[j])) + a.t[j];
+    for (int j = 0; j < 3; ++j) out[3 * i + j] = rigid_coord(x0, x1, x2, a.R, a.t, j);
+}
+
+// Viewer.rotate_trans_batch: ONE mesh under n rigid transforms, out (n,nv,3).  The table Rt (n,12) = [R row-major, t] is read
+// from DEVICE memory (block row k of the grid reads row k: uniform, scalar loads), so a captured graph replays with whatever
+// the table then holds.  View k equals rotate_translate_kernel with the same twelve numbers, bit for bit.
+__global__ void rigid_views_kernel(const float *__restrict__ x, long nv, const float *__restrict__ Rt, float *__restrict__ out)
+{
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nv) return;
+    const float *R = Rt + (size_t)blockIdx.y * 12;
+    const float x0 = x[3 * i], x1 = x[3 * i + 1], x2 = x[3 * i + 2];
+    float *o = out + ((size_t)blockIdx.y * nv + i) * 3;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) o[j] = rigid_coord(x0, x1, x2, R, R + 9, j);
 }
 
 }  // namespace
@@ -320,6 +340,18 @@ int lwg_rotate_translate(const float *x, long n, const float *R9, const float *t
     for (int i = 0; i < 3; ++i) a.t[i] = t3[i];
     rotate_translate_kernel<<<ceil_div(n, 256), 256, 0, as_stream(stream)>>>(x, n, a, out);
     LWG_LAUNCH_CHECK("rotate_translate_kernel");
+    return LWG_OK;
+}
+
+int lwg_rigid_views(const float *x, long nv, const float *Rt, int n, float *out, lwg_stream_t stream)
+{
+    LWG_REQUIRE(x && Rt && out, "rigid_views: NULL argument");
+    LWG_REQUIRE(n > 0 && nv > 0, "rigid_views: sizes must be positive (n=%d nv=%ld)", n, nv);
+    if (n > 65535) LWG_FAIL(LWG_ERR_UNSUPPORTED, "rigid_views: n=%d transforms exceed 65535 per launch", n);
+    if (nv > (1L << 31) - 256) LWG_FAIL(LWG_ERR_UNSUPPORTED, "rigid_views: nv=%ld exceeds the launch grid", nv);
+    const dim3 grid(ceil_div(nv, 256), n);
+    rigid_views_kernel<<<grid, 256, 0, as_stream(stream)>>>(x, nv, Rt, out);
+    LWG_LAUNCH_CHECK("rigid_views_kernel");
     return LWG_OK;
 }
 

@@ -35,6 +35,42 @@ def morph(src_bg_mask, ks, mode='erode', kernel=None, complement=False):
     return 1 - out if complement else out
 
 
+def image_grid_shape(n, H, W, nrow=8, padding=2):
+    """(grid_h, grid_w) of torchvision's make_grid for n images of H x W (lwg_image_grid_shape; needs no device)."""
+    import ctypes
+    from .. import _lib
+    gh, gw = ctypes.c_int(), ctypes.c_int()
+    _lib.check(_lib.load().lwg_image_grid_shape(int(n), int(H), int(W), int(nrow), int(padding), ctypes.byref(gh), ctypes.byref(gw)))
+    return gh.value, gw.value
+
+
+def image_grid_u8(x, nrow=8, padding=2, pad_value=0.0, normalize=False):
+    """torchvision.utils.make_grid + the uint8 conversion of save_image in one liblwg launch (lwg_image_grid_u8): x (n,3,H,W)
+    CUDA float tensor -> (grid_h, grid_w, 3) uint8 CUDA tensor, `uint8(clamp(v * 255 + 0.5, 0, 255))` with v = (x + 1) / 2 when
+    `normalize` (the reference's run_view.py:77) else x."""
+    from .. import _lib
+    if not x.is_cuda:
+        raise RuntimeError("image_grid_u8: the images must be a CUDA tensor (no CPU path)")
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError("image_grid_u8: (n, 3, H, W) expected, got %s" % (tuple(x.shape),))
+    x = x.float().contiguous()
+    n, _, h, w = x.shape
+    gh, gw = image_grid_shape(n, h, w, nrow, padding)
+    out = torch.empty((gh, gw, 3), device=x.device, dtype=torch.uint8)
+    _lib.check(_lib.load().lwg_image_grid_u8(_lib.ptr(x), n, h, w, int(nrow), int(padding), float(pad_value), int(bool(normalize)),
+                                             _lib.ptr(out), _lib.stream_ptr()))
+    return out
+
+
+def save_image_grid(x, path, nrow=8, padding=2, pad_value=0.0, normalize=False):
+    """torchvision.utils.save_image(x, path): the grid is laid out and converted on the device (image_grid_u8), its bytes come
+    back in ONE device->host copy and PIL writes them."""
+    from PIL import Image
+    grid = image_grid_u8(x, nrow=nrow, padding=padding, pad_value=pad_value, normalize=normalize)
+    Image.fromarray(grid.cpu().numpy()).save(path)
+    return grid
+
+
 def load_pickle_file(pkl_path):
     """utils/util.py:235-239."""
     with open(pkl_path, 'rb') as f:

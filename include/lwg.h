@@ -140,6 +140,10 @@ LWG_API int lwg_smpl_project_joints(const float *j3d, const float *cam, int bs, 
 /* Viewer.rotate_trans (models/viewer.py:240-247), `torch.bmm(X, R) + t` of the novel-view path: out (n,3) = x (n,3) @ R + t.
  * R9 (row-major 3x3) and t3 are HOST pointers (twelve floats, passed to the kernel by value); x / out device pointers. */
 LWG_API int lwg_rotate_translate(const float *x, long n, const float *R9, const float *t3, float *out, lwg_stream_t stream);
+/* The same mesh under n rigid transforms at once (a turntable of novel views): x (nv,3) -> out (n,nv,3), out[k] = x @ R_k + t_k.
+ * Rt (n,12) is a DEVICE array, row k = [R_k row-major (9), t_k (3)]: the kernel reads it, so a captured graph replays with
+ * whatever the table holds then.  out[k] is bit-identical to lwg_rotate_translate with the same twelve numbers.  n <= 65535. */
+LWG_API int lwg_rigid_views(const float *x, long nv, const float *Rt, int n, float *out, lwg_stream_t stream);
 LWG_API size_t lwg_smpl_workspace_bytes(int bs);
 LWG_API int lwg_smpl_forward(const float *theta, int bs, int num_betas, int nv, int num_out_joints,
                              const float *v_template, const float *shapedirs, const float *posedirs,
@@ -177,6 +181,17 @@ LWG_API int lwg_clamp(float *x, size_t n, float lo, float hi, lwg_stream_t strea
  * throughout, the library's bf16x3 arithmetic is narrower -- one probe pass in both arithmetics per weight set decides which one
  * serves it, and this is its `(a - b).abs().max()` without a framework kernel. */
 LWG_API int lwg_max_abs_diff(const float *a, const float *b, size_t n, float *out, lwg_stream_t stream);
+/* A batch of images as one uint8 picture: torchvision.utils.make_grid followed by save_image's conversion, which is how the
+ * reference's run_view.py:76-85 writes its novel views.  x (n,3,H,W) fp32 NCHW -> out (grid_h,grid_w,3) uint8 HWC.
+ *   layout: xmaps = min(nrow, n), ymaps = ceil(n / xmaps); grid_h = (H+padding)*ymaps + padding, grid_w = (W+padding)*xmaps +
+ *     padding; image k at row (k / xmaps)*(H+padding) + padding, column (k % xmaps)*(W+padding) + padding; pad_value everywhere
+ *     else, the cells of an incomplete last row included.  n == 1: the grid is the image itself, H x W, no padding.
+ *   value : v = normalize ? (p + 1) / 2 : p, then uint8(clamp(v * 255 + 0.5, 0, 255)) with truncation; every step a separately
+ *     rounded fp32 operation (no fused multiply-add).  pad_value takes the same conversion without the normalize step.
+ * lwg_image_grid_shape needs no device.  n, H, W, nrow <= 0 or padding < 0: LWG_ERR_INVALID_ARG. */
+LWG_API int lwg_image_grid_shape(int n, int H, int W, int nrow, int padding, int *grid_h, int *grid_w);
+LWG_API int lwg_image_grid_u8(const float *x, int n, int H, int W, int nrow, int padding, float pad_value, int normalize,
+                              unsigned char *out, lwg_stream_t stream);
 /* ---- Once-per-source glue of Imitator.personalize (models/imitator.py:82-155), so that `personalize` launches no
  * framework kernel.
  * morph: utils/util.py:73-89 -- erode (mode 0: pad with 1, count == ks*ks) / dilate (mode 1: pad with 0, count >= 1) of a
