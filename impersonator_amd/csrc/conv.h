@@ -109,7 +109,8 @@ struct StemArgs {
 };
 bool stem_bf16x3_supported(int H, int W, int cin, int cin_pad, int cout, int k, int stride, int pad);
 void stem_pack_weights(const float *w_oihw, int cin, std::vector<unsigned char> &out);
-int launch_stem_bf16x3(const StemArgs &a, hipStream_t st);
+// max_workgroups > 0 caps the persistent grid (0: one workgroup per CU, what the generator asks for); the schedule changes no bit
+int launch_stem_bf16x3(const StemArgs &a, hipStream_t st, int max_workgroups = 0);
 
 // (mean, M2) partials -> per (image, channel) scale/shift of InstanceNorm2d(affine, eps) (biased variance)
 int launch_in_finalize(const float2 *partials, int nphase, int mtiles, int N, int C, const float *gamma,
@@ -150,6 +151,7 @@ int launch_heads(const HeadsArgs &a, hipStream_t st);
 // launch_heads_pack(wh [49][64][4], wfrag) (heads_bf16x3_frag_bytes() bytes, device)
 size_t heads_bf16x3_frag_bytes();
 int launch_heads_pack(const float *wh, void *wfrag, hipStream_t st);
-int launch_heads_bf16x3(const HeadsArgs &a, const void *wfrag, hipStream_t st);
+// bands > 0 forces that many row bands per strip (0: the launcher's choice from the CU count, what the generator asks for)
+int launch_heads_bf16x3(const HeadsArgs &a, const void *wfrag, hipStream_t st, int bands = 0);
 
 }  // namespace lwg

@@ -285,9 +285,10 @@ void stem_pack_weights(const float *w, int cin, std::vector<unsigned char> &out)
                 }
 }
 
-int launch_stem_bf16x3(const StemArgs &a, hipStream_t st)
+int launch_stem_bf16x3(const StemArgs &a, hipStream_t st, int max_workgroups)
 {
     if (!a.x || !a.w || !a.y) LWG_FAIL(LWG_ERR_INVALID_ARG, "stem: NULL argument");
+    if (a.N < 1 || a.H < 1 || a.W < 1 || max_workgroups < 0) LWG_FAIL(LWG_ERR_INVALID_ARG, "stem: empty tensor or negative grid cap");
     if (a.W % ST_COLS || a.H % ST_ROWS) LWG_FAIL(LWG_ERR_UNSUPPORTED, "stem: %dx%d is not a multiple of the 2x128 tile", a.H, a.W);
     static DeviceOnce opt_in;
     if (!opt_in.done()) {
@@ -297,7 +298,9 @@ int launch_stem_bf16x3(const StemArgs &a, hipStream_t st)
     }
     const int ncu = device_cu_count();
     const int ntiles = a.N * (a.H / ST_ROWS) * (a.W / ST_COLS);
-    const int want = ceil_div(ntiles, ST_GROUPS), nwg = want < ncu ? want : ncu;
+    const int want = ceil_div(ntiles, ST_GROUPS);
+    int nwg = want < ncu ? want : ncu;
+    if (max_workgroups > 0 && nwg > max_workgroups) nwg = max_workgroups;   // tests: more tiles per group than the default grid gives
 #ifdef LWG_EXPERIMENTS
     static const int dbg = getenv("LWG_STEM_DBG") ? atoi(getenv("LWG_STEM_DBG")) : 0;
     StemArgs b = a;
@@ -311,3 +314,73 @@ int launch_stem_bf16x3(const StemArgs &a, hipStream_t st)
 }
 
 }  // namespace lwg
+
+using namespace lwg;
+
+// Diagnostic entry (include/lwg.h): the generator's 7x7 stem on its own, through the launch code run_conv (generator.hip) uses.
+int lwg_stem_forward(const float *x, int N, int H, int W, const float *w_host, int cin, int precision, float *y, float *partials,
+                     int max_workgroups, lwg_stream_t stream)
+{
+    LWG_REQUIRE(x && w_host && y, "stem_forward: NULL argument");
+    LWG_REQUIRE(N >= 1 && H >= 1 && W >= 1, "stem_forward: empty tensor (N=%d, H=%d, W=%d)", N, H, W);
+    LWG_REQUIRE(cin >= 1, "stem_forward: cin=%d", cin);
+    LWG_REQUIRE(precision == 0 || precision == 1, "stem_forward: precision=%d (0: fp32, 1: bf16x3)", precision);
+    LWG_REQUIRE(max_workgroups >= 0, "stem_forward: max_workgroups=%d", max_workgroups);
+    LWG_REQUIRE((uintptr_t)x % 16 == 0 && (uintptr_t)y % 4 == 0 && (uintptr_t)partials % 8 == 0,
+                "stem_forward: x must be 16-byte aligned (y 4, partials 8)");
+    if (cin > 6) LWG_FAIL(LWG_ERR_UNSUPPORTED, "stem_forward: cin=%d, the NHWC8 stem carries at most 6 channels", cin);
+    if (W % ST_COLS || H % ST_ROWS)
+        LWG_FAIL(LWG_ERR_UNSUPPORTED, "stem_forward: %dx%d is not a multiple of the %dx%d tile", H, W, ST_ROWS, ST_COLS);
+    if ((long)N * H * W > (1l << 24)) LWG_FAIL(LWG_ERR_UNSUPPORTED, "stem_forward: more than 2^24 pixels");
+    hipStream_t st = as_stream(stream);
+
+    ConvPhase ph = {};
+    ph.KH = ph.KW = 7;
+    ph.ntaps = 49;
+    ph.Kpad = (int)align_up((size_t)49 * 8, kConvBK);
+    std::vector<unsigned char> packed;
+    if (precision == 1) {
+        stem_pack_weights(w_host, cin, packed);
+    } else {
+        // upload_conv's layout (generator.hip): [cout][(kh*7 + kw) * 8 + ci], zero padded to Kpad
+        packed.assign((size_t)64 * ph.Kpad * sizeof(float), 0);
+        float *h = reinterpret_cast<float *>(packed.data());
+        for (int co = 0; co < 64; ++co)
+            for (int ci = 0; ci < cin; ++ci)
+                for (int t = 0; t < 49; ++t) h[(size_t)co * ph.Kpad + (size_t)t * 8 + ci] = w_host[((size_t)co * cin + ci) * 49 + t];
+    }
+    void *wdev = nullptr;
+    LWG_HIP(hipMalloc(&wdev, packed.size()));
+    int rc = LWG_OK;
+    if (hipMemcpy(wdev, packed.data(), packed.size(), hipMemcpyHostToDevice) != hipSuccess) {
+        set_error("stem_forward: weight upload failed");
+        rc = LWG_ERR_HIP;
+    } else if (precision == 1) {
+        StemArgs s = {};
+        s.x = x; s.N = N; s.H = H; s.W = W;
+        s.w = wdev;
+        s.y = y;
+        s.partials = reinterpret_cast<float2 *>(partials);
+        rc = launch_stem_bf16x3(s, st, max_workgroups);
+    } else {
+        ConvArgs a = {};
+        a.x = x; a.ldx = 8;
+        a.N = N; a.H = H; a.W = W; a.Cin = 8; a.cin_log2 = 3;
+        a.w = static_cast<const float *>(wdev);
+        a.y = y; a.ldy = 64;
+        a.Ho = a.Hm = H; a.Wo = a.Wm = W; a.Cout = 64;
+        a.stride = 1; a.pad = 3; a.os = 1; a.dil = 1;
+        a.partials = reinterpret_cast<float2 *>(partials);
+        a.mtiles = N * H * W / kConvBM;
+        a.nphase = 1;
+        a.ph[0] = ph;
+        rc = launch_conv_igemm(a, 64, st);
+    }
+    // the weights live for this call only: wait for the kernel that reads them
+    if (hipStreamSynchronize(st) != hipSuccess && rc == LWG_OK) {
+        set_error("stem_forward: the stem kernel failed");
+        rc = LWG_ERR_HIP;
+    }
+    (void)hipFree(wdev);
+    return rc;
+}

@@ -294,10 +294,11 @@ int launch_heads_pack(const float *wh, void *wfrag, hipStream_t st)
     return LWG_OK;
 }
 
-int launch_heads_bf16x3(const HeadsArgs &a, const void *wfrag, hipStream_t st)
+int launch_heads_bf16x3(const HeadsArgs &a, const void *wfrag, hipStream_t st, int bands_forced)
 {
     if (a.pred && !a.bg) LWG_FAIL(LWG_ERR_INVALID_ARG, "heads: pred requested without a background image");
     if (!wfrag) LWG_FAIL(LWG_ERR_STATE, "heads: packed weight fragments missing");
+    if (a.N < 1 || a.H < 1 || a.W < 1 || bands_forced < 0) LWG_FAIL(LWG_ERR_INVALID_ARG, "heads: empty tensor or negative band count");
     HeadsGeom g;
     g.strips = ceil_div(a.W, HS_OUT);
     // one wave per SIMD slot: aim at 4 waves per CU over the whole grid, bands of at least 8 output rows
@@ -305,6 +306,7 @@ int launch_heads_bf16x3(const HeadsArgs &a, const void *wfrag, hipStream_t st)
     int bands = target / (g.strips * a.N);
     if (bands < 1) bands = 1;
     if (bands > ceil_div(a.H, 8)) bands = ceil_div(a.H, 8);
+    if (bands_forced > 0) bands = bands_forced < a.H ? bands_forced : a.H;   // tests: band lengths the CU count would not pick
     g.band_rows = ceil_div(a.H, bands);
     g.bands = ceil_div(a.H, g.band_rows);
     heads_bf16x3_kernel<<<g.strips * g.bands * a.N, 64, 0, st>>>(a, static_cast<const uint4 *>(wfrag), g);

@@ -2685,6 +2685,50 @@ int lwg_heads_forward(const float *x, int N, int H, int W, const float *w, int w
     return launch_heads(h, st);
 }
 
+// Diagnostic entry (include/lwg.h): the heads as the inference path runs them (generator.hip: decode + heads), either arithmetic.
+size_t lwg_heads_inference_workspace_bytes(int N, int H, int W)
+{
+    if (N < 1 || H < 1 || W < 1) return 0;
+    return kHeadsWFloats * sizeof(float) + heads_bf16x3_frag_bytes();   // wh [49][64][4] | its bf16x3 B fragments
+}
+
+int lwg_heads_inference(const float *x, int N, int H, int W, const float *scale_shift, const float *w, int w_rows, int precision,
+                        const float *bg, int bg_bs, float *color, float *mask, float *pred, int bands, void *ws, size_t ws_bytes,
+                        lwg_stream_t stream)
+{
+    LWG_REQUIRE(x && scale_shift && w && ws && (color || mask || pred), "heads_inference: NULL argument");
+    LWG_REQUIRE(N >= 1 && H >= 1 && W >= 1, "heads_inference: empty tensor (N=%d, H=%d, W=%d)", N, H, W);
+    if (w_rows < 4) LWG_FAIL(LWG_ERR_INVALID_ARG, "heads_inference: the weight tensor needs >= 4 rows (3 colour + 1 mask), got %d", w_rows);
+    LWG_REQUIRE(precision == 0 || precision == 1, "heads_inference: precision=%d (0: fp32, 1: bf16x3)", precision);
+    LWG_REQUIRE(bands >= 0, "heads_inference: bands=%d", bands);
+    LWG_REQUIRE(!pred || bg, "heads_inference: pred requested without a background image");
+    LWG_REQUIRE(!bg || bg_bs == 1 || bg_bs == N, "heads_inference: bg_bs=%d, must be 1 or the batch size %d", bg_bs, N);
+    LWG_REQUIRE(((uintptr_t)x | (uintptr_t)ws) % 16 == 0 && (uintptr_t)scale_shift % 8 == 0,
+                "heads_inference: x and the workspace must be 16-byte aligned (scale_shift 8)");
+    if ((long)N * H * W > (1l << 24)) LWG_FAIL(LWG_ERR_UNSUPPORTED, "heads_inference: more than 2^24 pixels");
+    if (ws_bytes < lwg_heads_inference_workspace_bytes(N, H, W))
+        LWG_FAIL(LWG_ERR_WORKSPACE, "heads_inference: workspace of %zu bytes, %zu needed", ws_bytes,
+                 lwg_heads_inference_workspace_bytes(N, H, W));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    float *wh = static_cast<float *>(ws);
+    void *wfrag = wh + kHeadsWFloats;
+    heads_weight_kernel<<<ceil_div((long)kHeadsWFloats, 256), 256, 0, st>>>(w, wh);
+    LWG_LAUNCH_CHECK("heads_weight_kernel");
+    HeadsArgs h = {};
+    h.x = x; h.N = N; h.H = H; h.W = W;
+    h.scale_shift = reinterpret_cast<const float2 *>(scale_shift);
+    h.wh = wh;
+    h.color = color;
+    h.mask = mask;
+    h.bg = bg;
+    h.bg_bs = bg ? bg_bs : 1;
+    h.pred = pred;
+    if (precision == 0) return launch_heads(h, st);
+    const int rc = launch_heads_pack(wh, wfrag, st);
+    if (rc != LWG_OK) return rc;
+    return launch_heads_bf16x3(h, wfrag, st, bands);
+}
+
 int lwg_heads_backward_weight(const float *x, const float *dy8, int N, int H, int W, float *dw, void *ws, size_t ws_bytes,
                               lwg_stream_t stream)
 {

@@ -114,6 +114,48 @@ def heads_forward(x, w):
 
 
 @torch.no_grad()
+def heads_inference(x, scale_shift, w, precision="bf16x3", bg=None, outputs=("color", "mask", "pred"), bands=0):
+    """The inference path's heads on their own (lwg_heads_inference): x (N,H,W,64) RAW, scale_shift (N,64,2), w (>=4,64,7,7),
+    bg (1 or N,3,H,W) or None -> dict of the requested outputs: color (N,3,H,W) = tanh, mask (N,1,H,W) = sigmoid of the 7x7 conv of
+    relu(x * scale + shift), pred = mask*bg + (1-mask)*color.  bands > 0 forces the bf16x3 kernel's row bands (0: the launcher's
+    choice).  Outputs start as NaN, so a pixel the kernel does not write shows."""
+    _chk(x, scale_shift, w, bg)
+    n, h, wd, c = x.shape
+    if c != 64 or tuple(w.shape[1:]) != (64, 7, 7) or tuple(scale_shift.shape) != (n, 64, 2):
+        raise RuntimeError("heads_inference: x (N,H,W,64), scale_shift (N,64,2) and w (>=4,64,7,7) expected")
+    if bg is not None and (bg.shape[0] not in (1, n) or tuple(bg.shape[1:]) != (3, h, wd)):
+        raise RuntimeError("heads_inference: bg (1 or N,3,H,W) expected")
+    chans = {"color": 3, "mask": 1, "pred": 3}
+    out = {k: torch.full((n, chans[k], h, wd), float("nan"), device=x.device, dtype=torch.float32) for k in outputs}
+    lib = _lib.load()
+    nb = lib.lwg_heads_inference_workspace_bytes(n, h, wd)
+    ws = torch.empty(nb // 4 + 4, device=x.device, dtype=torch.float32)
+    _lib.check(lib.lwg_heads_inference(_lib.ptr(x), n, h, wd, _lib.ptr(scale_shift), _lib.ptr(w), int(w.shape[0]),
+                                       PRECISIONS[precision], _lib.ptr(bg), 1 if bg is None else int(bg.shape[0]),
+                                       _lib.ptr(out.get("color")), _lib.ptr(out.get("mask")), _lib.ptr(out.get("pred")), int(bands),
+                                       _lib.ptr(ws), nb, _lib.stream_ptr()))
+    return out
+
+
+@torch.no_grad()
+def stem_forward(x, w, precision="bf16x3", with_partials=True, max_workgroups=0):
+    """The generator's 7x7 stem on its own (lwg_stem_forward): x (N,H,W,8) NHWC8, w (64,cin,7,7) on the CPU (the entry point packs
+    and uploads it), cin <= 6 -> (y (N,H,W,64) raw, partials (N*H*W/128,64,2) = per-tile (mean, M2), or None).  max_workgroups > 0
+    caps the persistent grid of the bf16x3 kernel (0: the launcher's choice).  Outputs start as NaN."""
+    _chk(x)
+    if w.is_cuda or w.dtype != torch.float32 or not w.is_contiguous():
+        raise RuntimeError("stem_forward: w is a contiguous float32 CPU tensor")
+    n, h, wd, c = x.shape
+    if c != 8 or w.shape[0] != 64 or tuple(w.shape[2:]) != (7, 7):
+        raise RuntimeError("stem_forward: x (N,H,W,8) and w (64,cin,7,7) expected")
+    y = torch.full((n, h, wd, 64), float("nan"), device=x.device, dtype=torch.float32)
+    partials = torch.full((n * h * wd // 128, 64, 2), float("nan"), device=x.device, dtype=torch.float32) if with_partials else None
+    _lib.check(_lib.load().lwg_stem_forward(_lib.ptr(x), n, h, wd, _lib.ptr(w), int(w.shape[1]), PRECISIONS[precision], _lib.ptr(y),
+                                            _lib.ptr(partials), int(max_workgroups), _lib.stream_ptr()))
+    return y, partials
+
+
+@torch.no_grad()
 def heads_backward_weight(x, dy8, out=None):
     """x (N,H,W,64), dy8 (N,H,W,8) (gradient wrt the pre-activation head outputs, channels 4-7 zero) -> dw (8,64,7,7)."""
     _chk(x, dy8)

@@ -450,6 +450,40 @@ LWG_API int lwg_heads_forward(const float *x, int N, int H, int W, const float *
 LWG_API int lwg_heads_backward_weight(const float *x, const float *dy8, int N, int H, int W, float *dw, void *workspace,
                                       size_t workspace_bytes, lwg_stream_t stream);
 
+/* Diagnostic entries (as lwg_inpaint_attention: for tests, not a hot path): the two direct kernels of the default bf16x3 inference
+ * path on their own, through the launch code lwg_generator_inference runs, so that they can be held against float64 at shapes the
+ * whole generator never gives them.  Every argument is checked before the first HIP call.
+ *
+ * lwg_stem_forward: the generator's first layer, Conv2d(cin -> 64, k7, s1, p3, no bias), on an NHWC8 input.
+ *   x (N,H,W,8) fp32, 16-byte aligned; channels cin..7 are never read as data (channels 6-7 not at all; cin..5 meet zero weights),
+ *     but EVERY value of channels 0..5 must be finite: the padded tail of a 48-entry run multiplies the next pixel's channels by
+ *     zero weights, so a NaN / Inf pixel reaches outputs outside its 7x7 footprint (precision 1);
+ *   w_host (64,cin,7,7) in HOST memory, PyTorch layout, 1 <= cin <= 6: packed and uploaded as lwg_generator_load_weight does;
+ *   precision 1: stem_bf16x3_kernel (W % 128 == 0, H % 2 == 0, else LWG_ERR_UNSUPPORTED); precision 0: the exact-fp32 small-Cin
+ *     implicit GEMM on the same arguments -- what the generator runs under lwg_generator_set_precision(g, 0);
+ *   y (N,H,W,64) raw (pre-norm) output; partials (N*H*W/128, 64, 2) or NULL: (mean, M2) of y per channel over each run of 128
+ *     consecutive pixels, the InstanceNorm statistics the generator reduces further;
+ *   max_workgroups: 0 = the launcher's grid (one persistent workgroup per CU, at most one per two tiles), what the generator uses;
+ *     > 0 caps it, so that a small tensor gives each four-wave group several tiles.  The schedule changes no result bit.
+ *   Allocates and frees the device copy of the weights and synchronises the stream: not for a captured graph.
+ *
+ * lwg_heads_inference: tanh / sigmoid of Conv2d(64 -> 3 + 1, k7, p3, no bias) on relu(x * scale + shift), zero padding applied
+ *   AFTER the normalisation (a padded tap contributes 0, not relu(shift)), plus the blend of Imitator.forward.
+ *   x (N,H,W,64) raw fp32, 16-byte aligned; scale_shift (N,64,2) = (scale, shift) per image and channel; w (w_rows >= 4,64,7,7) on
+ *     the DEVICE, rows 0-2 colour, row 3 mask, further rows ignored; any N, H, W >= 1;
+ *   precision 0: heads_kernel (exact fp32, vector ALU); 1: heads_bf16x3_kernel (matrix cores, hardware exp / rcp activations);
+ *   bg (bg_bs,3,H,W) with bg_bs in {1, N} or NULL; outputs, each optional but one required: color (N,3,H,W), mask (N,1,H,W),
+ *     pred (N,3,H,W) = mask*bg + (1-mask)*color (needs bg);
+ *   bands (precision 1 only): 0 = the launcher's choice of row bands per 26-column strip from the CU count, what the generator
+ *     uses; > 0 forces min(bands, H) bands of ceil(H / bands) rows.  An output row's bits do not depend on the banding.
+ *   workspace: lwg_heads_inference_workspace_bytes, 16-byte aligned, scratch only.  Enqueued on the stream, no synchronisation. */
+LWG_API int lwg_stem_forward(const float *x, int N, int H, int W, const float *w_host, int cin, int precision, float *y,
+                             float *partials, int max_workgroups, lwg_stream_t stream);
+LWG_API size_t lwg_heads_inference_workspace_bytes(int N, int H, int W);
+LWG_API int lwg_heads_inference(const float *x, int N, int H, int W, const float *scale_shift, const float *w, int w_rows,
+                                int precision, const float *bg, int bg_bs, float *color, float *mask, float *pred, int bands,
+                                void *workspace, size_t workspace_bytes, lwg_stream_t stream);
+
 /* Generator-side adversarial term (models/impersonator_trainer.py:369-371): loss = mean((D(x) - target)^2) on
  * x (bs,input_nc,is,is) NCHW and its gradient wrt x (same shape); the discriminator's parameters get no gradient. */
 LWG_API int lwg_discriminator_input_grad(lwg_discriminator *d, const float *x_nchw, int bs, float target, float *loss_device,

@@ -320,3 +320,132 @@ def split_bf16_decode(buf):
     N, C = buf.shape
     h = buf.contiguous().view(torch.bfloat16).view(N, C // 32, 2, 32)
     return h[:, :, 0].reshape(N, C), h[:, :, 1].reshape(N, C)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The two direct kernels of the bf16x3 inference path on their own (lwg_stem_forward, lwg_heads_inference): seeded inputs, the
+# float64 references and a float64 restatement of the split arithmetic.  tests/test_direct_cases.py proves on the CPU that the
+# restatement sits inside a third of every bound tests/test_gpu_direct_kernels.py holds the kernels to.
+BF16X3_REL = 3e-5        # bf16x3 against float64, relative to max |reference| (the bound of tests/test_gpu_ops.py)
+FP32_REL = 1e-5          # exact-fp32 kernels, same convention (tests/test_gpu_ops.py)
+ACT_ABS = 1e-5           # tanh / sigmoid allowance of test_heads_ops; also the whole fp32 heads bound
+# (mean, M2) partials of the stem: relative error of the restatement's M2 per 128-pixel tile against float64, relative to
+# max |M2|, measured over STEM_CASES (test_direct_cases.py prints it per case and asserts that none exceeds this figure):
+STEM_M2_MEASURED = 2.2e-6   # 1.74e-6 to 2.17e-6 over the five cases, the worst on (2,8,384)
+STEM_M2_REL = 10 * STEM_M2_MEASURED
+
+# (N, H, W, cin, grids): grids = the max_workgroups values to run (0: the launcher's own grid)
+STEM_CASES = [
+    (1, 2, 128, 6, (0,)),        # one tile, every pixel at a border, the workgroup's second four-wave group idle
+    (1, 6, 128, 6, (1,)),        # three tiles on one workgroup: group 0 walks two, group 1 one
+    (1, 6, 128, 3, (1,)),        # cin 3: the filter bank's entries of the missing channels stay zero
+    (3, 4, 256, 6, (1, 2, 0)),   # six / three tiles per group, tiles cross image boundaries, a real left halo
+    (2, 8, 384, 6, (0,)),        # three tiles per row
+]
+# (N, H, W, w_rows, bands tuple)
+HEADS_CASES = [(2, H, 27, 4, (0,)) for H in range(1, 9)] + [   # one band of H rows: every residue of the accumulator ring's last slot;
+                                                               # the second strip owns a single column
+    (2, 8, 26, 8, (0,)),          # exactly one strip; weight rows 4-7 hold garbage
+    (2, 8, 5, 4, (0,)),           # narrower than the kernel
+    (3, 45, 104, 8, (4, 1, 0)),   # bands of 12, 12, 12, 9 rows / one band of 51 steps (six ring laps) / the launcher's choice
+    (2, 24, 64, 4, (3, 0)),       # band edges on multiples of 8
+]
+
+
+def bf16_split(v):
+    """fp32 tensor -> (hi, lo) as float64: hi = bf16(v), lo = bf16(v - hi), round to nearest even like the hardware conversion."""
+    v = v.float()
+    hi = v.to(torch.bfloat16)
+    lo = (v - hi.float()).to(torch.bfloat16)
+    return hi.double(), lo.double()
+
+
+def conv7_bf16x3(x, w, drop=None):
+    """The split arithmetic restated in float64: 7x7 / pad 3 convolution of x (N,C,H,W) with w (O,C,7,7), both fp32, as
+    lo*hi + hi*lo + hi*hi of their bf16 halves (every product exact, sums in float64).  drop: 'lo_hi' / 'hi_lo' leaves that cross
+    product out (a mutant for the sensitivity checks)."""
+    import torch.nn.functional as F
+    xh, xl = bf16_split(x)
+    wh, wl = bf16_split(w)
+    y = F.conv2d(xh, wh, None, 1, 3)
+    if drop != "lo_hi":
+        y = y + F.conv2d(xl, wh, None, 1, 3)
+    if drop != "hi_lo":
+        y = y + F.conv2d(xh, wl, None, 1, 3)
+    return y
+
+
+@functools.lru_cache(maxsize=None)
+def stem_case(N, H, W, cin):
+    """Seeded inputs and the float64 reference of one stem case (shared: treat as read-only).  x8 (N,H,W,8): uniform [-1,1] in
+    channels 0..cin-1, non-zero finite garbage in every other channel (6-7 are never read, cin..5 meet zero weights); w 0.05 randn.
+    ref (N,H,W,64) float64 = F.conv2d; mean / m2 (N*H*W/128, 64): float64 statistics of ref over each run of 128 pixels."""
+    import torch.nn.functional as F
+    g = torch.Generator().manual_seed(4000 + 97 * N + 13 * H + W + cin)
+    x8 = (torch.rand(N, H, W, 8, generator=g) + 0.5) * 1000.0 * (torch.randint(0, 2, (N, H, W, 8), generator=g) * 2 - 1).float()
+    x8[..., :cin] = torch.rand(N, H, W, cin, generator=g) * 2 - 1
+    w = torch.randn(64, cin, 7, 7, generator=g) * 0.05
+    xc = x8[..., :cin].permute(0, 3, 1, 2).contiguous()
+    ref = F.conv2d(xc.double(), w.double(), None, 1, 3).permute(0, 2, 3, 1).contiguous()
+    tiles = ref.reshape(-1, 128, 64)
+    mean = tiles.mean(1)
+    m2 = ((tiles - mean[:, None]) ** 2).sum(1)
+    return dict(x8=x8, x=xc, w=w, ref=ref, mean=mean, m2=m2, N=N, H=H, W=W, cin=cin)
+
+
+def tile_stats(y):
+    """(N,H,W,64) -> float64 (mean, M2) per run of 128 consecutive pixels: the mtile = pixel / 128 order of launch_in_finalize."""
+    tiles = y.double().reshape(-1, 128, 64)
+    mean = tiles.mean(1)
+    return mean, ((tiles - mean[:, None]) ** 2).sum(1)
+
+
+def heads_activation(x, ss, dtype):
+    """relu(x * scale + shift) as (N,64,H,W).  float64: exactly; float32: one rounding of the exact product-sum, i.e. fmaf."""
+    v = x.double() * ss[:, None, None, :, 0].double() + ss[:, None, None, :, 1].double()
+    return v.to(dtype).clamp(min=0).permute(0, 3, 1, 2).contiguous()
+
+
+def heads_outputs(pre, bg):
+    """pre (N,4,H,W) float64 -> dict(pre, color, mask, pred): tanh, sigmoid and the blend mask*bg + (1-mask)*color."""
+    color, mask = torch.tanh(pre[:, 0:3]), torch.sigmoid(pre[:, 3:4])
+    return dict(pre=pre, color=color, mask=mask, pred=mask * bg.double() + (1 - mask) * color)
+
+
+@functools.lru_cache(maxsize=None)
+def heads_case(N, H, W, w_rows):
+    """Seeded inputs and the float64 reference of one heads case (shared: treat as read-only).  x (N,H,W,64) randn; ss (N,64,2) =
+    (scale randn -- negative ones included, shift 0.5 randn -- positive ones included, so padding with relu(shift) instead of 0
+    shows); w (w_rows,64,7,7): rows 0-3 0.03 randn, further rows garbage; bg (N,3,H,W) uniform [-1,1].  ref: heads_outputs of the
+    float64 F.conv2d on the float64 activation."""
+    import torch.nn.functional as F
+    g = torch.Generator().manual_seed(5000 + 977 * N + 131 * H + 7 * W + w_rows)
+    x = torch.randn(N, H, W, 64, generator=g)
+    ss = torch.stack([torch.randn(N, 64, generator=g), 0.5 * torch.randn(N, 64, generator=g)], dim=-1).contiguous()
+    w = torch.randn(w_rows, 64, 7, 7, generator=g) * 7.0
+    w[:4] = torch.randn(4, 64, 7, 7, generator=g) * 0.03
+    bg = torch.rand(N, 3, H, W, generator=g) * 2 - 1
+    pre = F.conv2d(heads_activation(x, ss, torch.float64), w[:4].double(), None, 1, 3)
+    return dict(x=x, ss=ss, w=w, bg=bg, ref=heads_outputs(pre, bg), N=N, H=H, W=W)
+
+
+def heads_restatement(case, drop=None, pad_relu_shift=False):
+    """heads_outputs of the bf16x3 restatement: conv7_bf16x3 on relu(fmaf(x, scale, shift)) in fp32.  pad_relu_shift: the mutant
+    that normalises the zero padding too (a padded tap contributes relu(shift) instead of 0), in exact float64."""
+    import torch.nn.functional as F
+    if pad_relu_shift:
+        a = heads_activation(case["x"], case["ss"], torch.float64)
+        N, C, H, W = a.shape
+        padded = case["ss"][:, :, 1].double().clamp(min=0)[:, :, None, None].expand(N, C, H + 6, W + 6).clone()
+        padded[:, :, 3:-3, 3:-3] = a
+        return heads_outputs(F.conv2d(padded, case["w"][:4].double()), case["bg"])
+    return heads_outputs(conv7_bf16x3(heads_activation(case["x"], case["ss"], torch.float32), case["w"][:4], drop), case["bg"])
+
+
+def heads_bounds(case, precision):
+    """(colour bound, mask bound) absolute: |tanh'| <= 1, |sigmoid'| <= 1/4 on the pre-activation bound, plus the activation
+    allowance; the exact-fp32 kernel keeps the 1e-5 of test_heads_ops."""
+    if precision == "fp32":
+        return ACT_ABS, ACT_ABS
+    pre_max = float(case["ref"]["pre"].abs().max())
+    return BF16X3_REL * pre_max + ACT_ABS, BF16X3_REL * pre_max / 4 + ACT_ABS

@@ -67,6 +67,36 @@ def test_argument_validation_without_a_device():
     assert attn(p, p, p, 1024, 1, 64, 0, p, p, big) == UNSUPPORTED    # 16 keys per chunk: less than a tile
     assert b"key chunks" in lib.lwg_last_error()
     assert attn(p, p, p, 1024, 1, 0, 0, p, p, ws_bytes(1024, 1, 0) - 1) == WORKSPACE
+    # lwg_stem_forward (x, N, H, W, w_host, cin, precision, y, partials, max_workgroups, stream): refusals before any HIP call
+    stem = lib.lwg_stem_forward
+    assert stem(p, 1, 2, 128, None, 6, 1, p, p, 0, None) == INVALID and b"NULL" in lib.lwg_last_error()
+    assert stem(None, 1, 2, 128, p, 6, 1, p, p, 0, None) == INVALID
+    assert stem(p, 1, 2, 128, p, 6, 1, None, p, 0, None) == INVALID
+    for n, h, w in ((0, 2, 128), (1, 0, 128), (1, 2, 0), (-1, 2, 128)):
+        assert stem(p, n, h, w, p, 6, 1, p, None, 0, None) == INVALID
+    assert stem(p, 1, 2, 128, p, 0, 1, p, None, 0, None) == INVALID          # cin < 1
+    assert stem(p, 1, 2, 128, p, 6, 2, p, None, 0, None) == INVALID          # no such precision
+    assert stem(p, 1, 2, 128, p, 6, 1, p, None, -1, None) == INVALID         # negative grid cap
+    assert stem(ctypes.c_void_p(4104), 1, 2, 128, p, 6, 1, p, None, 0, None) == INVALID   # float4 loads of x
+    assert b"aligned" in lib.lwg_last_error()
+    for precision in (0, 1):
+        assert stem(p, 1, 2, 128, p, 7, precision, p, None, 0, None) == UNSUPPORTED   # NHWC8 carries six channels
+        assert stem(p, 1, 2, 192, p, 6, precision, p, None, 0, None) == UNSUPPORTED   # W % 128
+        assert stem(p, 1, 3, 128, p, 6, precision, p, None, 0, None) == UNSUPPORTED   # H % 2
+    assert b"tile" in lib.lwg_last_error()
+    # lwg_heads_inference (x, N, H, W, scale_shift, w, w_rows, precision, bg, bg_bs, color, mask, pred, bands, ws, bytes, stream)
+    hws = lib.lwg_heads_inference_workspace_bytes
+    assert hws(2, 8, 27) == 49 * 64 * 4 * 4 + 28 * 2 * 64 * 16 and hws(0, 8, 27) == 0 and hws(2, 8, -1) == 0
+    heads = lambda x=p, n=2, h=8, w=27, ss=p, wt=p, rows=4, prec=1, bg=p, bg_bs=2, c=p, m=p, pr=p, bands=0, ws=p, nb=big: \
+        lib.lwg_heads_inference(x, n, h, w, ss, wt, rows, prec, bg, bg_bs, c, m, pr, bands, ws, nb, None)
+    for kw in (dict(x=None), dict(ss=None), dict(wt=None), dict(ws=None), dict(c=None, m=None, pr=None)):
+        assert heads(**kw) == INVALID and b"NULL" in lib.lwg_last_error(), kw
+    for kw in (dict(n=0), dict(h=0), dict(w=-3), dict(rows=3), dict(prec=2), dict(bands=-1), dict(bg=None), dict(bg_bs=3),
+               dict(bg_bs=0), dict(x=ctypes.c_void_p(4104)), dict(ws=ctypes.c_void_p(4104))):
+        assert heads(**kw) == INVALID, kw
+    assert heads(bg=None) == INVALID and b"background" in lib.lwg_last_error()                  # pred without bg
+    assert heads(nb=hws(2, 8, 27) - 1) == WORKSPACE
+    assert heads(prec=0, nb=hws(2, 8, 27) - 1) == WORKSPACE
 
 
 def test_product_path_fails_loudly_without_gpu():
