@@ -50,6 +50,18 @@ struct DeviceOnce {
     void mark() { done_mask |= 1ull << device(); }
 };
 
+// gfx950 has 160 KiB of LDS per CU: the most a kernel can be opted in to (above the 64 KiB a launch may ask for by default)
+constexpr size_t kLdsPerCu = 160 * 1024;
+
+// raises `kernel`'s dynamic-LDS ceiling to `bytes`, once per device.  Only a ceiling: occupancy follows the bytes of each launch.
+inline int opt_in_lds(const void *kernel, size_t bytes, DeviceOnce &once)
+{
+    if (once.done()) return LWG_OK;
+    LWG_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    once.mark();
+    return LWG_OK;
+}
+
 // compute-unit count of the current device (cached per device)
 inline int device_cu_count()
 {

@@ -1836,19 +1836,87 @@ int conv_trace_launch(int idx, long long *v)
     return LWG_OK;
 }
 
-// record block for one traced launch of `waves`-wave workgroups on grid (gx, gy); null when tracing is off or the buffer is full
-static unsigned long long *trace_block(const ConvArgs &a, int gx, int gy, int waves, int stages)
+// record block for one traced launch of `waves`-wave workgroups on `grid`; null when tracing is off or the buffer is full
+static unsigned long long *trace_block(const ConvArgs &a, dim3 grid, int waves, int stages)
 {
     if (!g_trace.buf) return nullptr;
-    const size_t need = (size_t)gx * gy * waves * 8 * sizeof(unsigned long long);
+    const size_t need = (size_t)grid.x * grid.y * grid.z * waves * 8 * sizeof(unsigned long long);
     if (g_trace.used + need > g_trace.bytes || g_trace.n >= kTraceMaxLaunches) return nullptr;
     unsigned long long *p = reinterpret_cast<unsigned long long *>(static_cast<char *>(g_trace.buf) + g_trace.used);
     TraceLaunch &L = g_trace.launch[g_trace.n++];
-    L.offset = g_trace.used; L.gx = gx; L.gy = gy; L.gz = 1; L.waves = waves; L.stages = stages; L.cin = a.Cin; L.cout = a.Cout;
-    L.hm = a.Hm; L.n = a.N;
+    L.offset = g_trace.used; L.gx = grid.x; L.gy = grid.y; L.gz = grid.z; L.waves = waves; L.stages = stages; L.cin = a.Cin;
+    L.cout = a.Cout; L.hm = a.Hm; L.n = a.N;
     g_trace.used += need;
     return p;
 }
+
+// ---- the conv kernels of the product: one row per instantiation, with the dynamic LDS it is opted in to on the first conv
+// launch on a device (the most a launch of it may ask for), the variant it reports and the label of its launch check
+struct ConvKernel { void (*fn)(ConvArgs); int block; size_t lds_cap; int variant; const char *label; };
+
+constexpr int kRawMaxChannels = 512;   // raw-input 3x3 halo kernels: the (scale, shift) table they are opted in for
+constexpr size_t reg_lds(int bn) { return (size_t)2 * (BM + bn) * LDK * sizeof(float); }                 // register-staged: two stages
+constexpr size_t ring_lds(int ns, int bn, int bmt = BM) { return (size_t)ns * (bmt + bn) * BK * sizeof(float); }   // DMA ring of ns slots
+// halo kernels: two halo slices of `hp` pixels in 8-pixel chunks + ns weight stages; RAW adds a staging row and the table
+constexpr size_t halo_lds(int hp, int ns, int bn) { return ((size_t)2 * ((hp + 7) / 8) * 8 * BK + (size_t)ns * bn * BK) * sizeof(float); }
+constexpr int halo3x3_px(int bmt) { return (bmt / 32 + 2) * (32 + 2); }
+constexpr int kHaloCTPx = (4 + 1) * (32 + 1);
+constexpr size_t raw_lds(int channels) { return (size_t)8 * BK * sizeof(float) + (size_t)channels * sizeof(float2); }
+
+enum ConvKernelId {
+    kF32_64, kF32_128, kF32_Small, kGen_64, kGen_128, kGen_Small, kGenX3_64, kGenX3_128, kGenX3_Small,
+    kDma_32, kDma_64, kDma_128,
+    kRing_64, kRing_128_3, kRing_128_4, kRing_128_Traced, kRing_128_Tall,
+    kHalo_64, kHalo_128, kHalo_Tall, kHaloRaw_64, kHaloRaw_128, kHaloRaw_Tall,
+    kHaloCT_64, kHaloCT_128, kHaloCTRaw_64, kHaloCTRaw_128,
+#ifdef LWG_EXPERIMENTS   // builds for profiles/r03_conv_experiments.md only (hipcc -DLWG_EXPERIMENTS): never in the shipped library
+    kRing_128_X, kRing_128_5,
+#endif
+    kConvKernels
+};
+static const ConvKernel kConvKernelTable[kConvKernels] = {
+    {&conv_igemm_f32<64, 1, 2, false>, 256, reg_lds(64), kIgemmReg64, "conv_igemm_f32"},
+    // the 128-channel tile needs 72 KiB of LDS: above the 64 KiB default, well inside gfx950's 160 KiB per CU
+    {&conv_igemm_f32<128, 2, 2, false>, 256, reg_lds(128), kIgemmReg128, "conv_igemm_f32"},
+    {&conv_igemm_f32<64, 1, 2, true>, 256, reg_lds(64), kIgemmSmallCin, "conv_igemm_f32"},
+    {&conv_igemm_f32<64, 1, 2, false, 0, true>, 256, reg_lds(64), kIgemmReg64, "conv_igemm_f32 (general)"},
+    {&conv_igemm_f32<128, 2, 2, false, 0, true>, 256, reg_lds(128), kIgemmReg128, "conv_igemm_f32 (general)"},
+    {&conv_igemm_f32<64, 1, 2, true, 0, true>, 256, reg_lds(64), kIgemmSmallCin, "conv_igemm_f32 (general)"},
+    // plain fp32 operands, split in the kernel
+    {&conv_igemm_f32<64, 1, 2, false, 0, true, true>, 256, reg_lds(64), kIgemmReg64, "conv_igemm_f32 (general)"},
+    {&conv_igemm_f32<128, 2, 2, false, 0, true, true>, 256, reg_lds(128), kIgemmReg128, "conv_igemm_f32 (general)"},
+    {&conv_igemm_f32<64, 1, 2, true, 0, true, true>, 256, reg_lds(64), kIgemmSmallCin, "conv_igemm_f32 (general)"},
+    // exact fp32, DMA-fed 3-stage ring: (BM + bn) * 32 floats per stage
+    {&conv_igemm_dma_f32<32, 1, 1>, 256, ring_lds(3, 32), kIgemmDma32, "conv_igemm_dma_f32"},
+    {&conv_igemm_dma_f32<64, 1, 2>, 256, ring_lds(3, 64), kIgemmDma64, "conv_igemm_dma_f32"},
+    {&conv_igemm_dma_f32<128, 2, 2>, 256, ring_lds(3, 128), kIgemmDma128, "conv_igemm_dma_f32"},
+    // bf16x3 on split operands: DMA-fed ring of (rows + bn) 128-byte rows per slot
+    {&conv_igemm_bf16x3<64, 1, 2>, 256, ring_lds(3, 64), kIgemmBf16x3_64, "conv_igemm_bf16x3"},
+    {&conv_igemm_bf16x3<128, 2, 2>, 256, ring_lds(3, 128), kIgemmBf16x3_128, "conv_igemm_bf16x3"},
+    {&conv_igemm_bf16x3<128, 2, 2, 4>, 256, ring_lds(4, 128), kIgemmBf16x3_128, "conv_igemm_bf16x3"},
+    {&conv_igemm_bf16x3<128, 2, 2, 4, 512>, 256, ring_lds(4, 128), kIgemmBf16x3_128, "conv_igemm_bf16x3 (traced)"},
+    {&conv_igemm_bf16x3<128, 2, 2, 3, 0, 256>, 512, ring_lds(3, 128, 256), kIgemmBf16x3_128, "conv_igemm_bf16x3 (256-row tiles)"},
+    // halo-resident 3x3 / stride 1 / pad 1 (the 64-channel tile is 52 + 24 KiB: two workgroups per CU)
+    {&conv3x3_halo_bf16x3<64, 1, 2, 3, 32>, 256, halo_lds(halo3x3_px(128), 3, 64), kHaloBf16x3_64, "conv3x3_halo_bf16x3"},
+    {&conv3x3_halo_bf16x3<128, 2, 2, 4, 32>, 256, halo_lds(halo3x3_px(128), 4, 128), kHaloBf16x3_128, "conv3x3_halo_bf16x3"},
+    {&conv3x3_halo_bf16x3<128, 2, 2, 4, 32, 256>, 512, halo_lds(halo3x3_px(256), 4, 128), kHaloBf16x3_128, "conv3x3_halo_bf16x3"},
+    // the input's InstanceNorm + ReLU + split folded into the halo (see HaloSched): the table is sized per launch
+    {&conv3x3_halo_bf16x3<64, 1, 2, 3, 32, 128, 0, true>, 256, halo_lds(halo3x3_px(128), 3, 64) + raw_lds(kRawMaxChannels),
+     kHaloBf16x3_64, "conv3x3_halo_bf16x3"},
+    {&conv3x3_halo_bf16x3<128, 2, 2, 4, 32, 128, 0, true>, 256, halo_lds(halo3x3_px(128), 4, 128) + raw_lds(kRawMaxChannels),
+     kHaloBf16x3_128, "conv3x3_halo_bf16x3"},
+    {&conv3x3_halo_bf16x3<128, 2, 2, 4, 32, 256, 0, true>, 512, halo_lds(halo3x3_px(256), 4, 128) + raw_lds(kRawMaxChannels),
+     kHaloBf16x3_128, "conv3x3_halo_bf16x3"},
+    // ConvTranspose2d(k3, s2, p1, op1) given as its four phases: one launch of the halo kernel (CT = 1)
+    {&conv3x3_halo_bf16x3<64, 1, 2, 3, 32, 128, 1>, 256, halo_lds(kHaloCTPx, 3, 64), kHaloBf16x3_64, "conv3x3_halo_bf16x3 (transposed)"},
+    {&conv3x3_halo_bf16x3<128, 2, 2, 4, 32, 128, 1>, 256, halo_lds(kHaloCTPx, 4, 128), kHaloBf16x3_128, "conv3x3_halo_bf16x3 (transposed)"},
+    {&conv3x3_halo_bf16x3<64, 1, 2, 3, 32, 128, 1, true>, 256, kLdsPerCu, kHaloBf16x3_64, "conv3x3_halo_bf16x3 (transposed)"},
+    {&conv3x3_halo_bf16x3<128, 2, 2, 4, 32, 128, 1, true>, 256, kLdsPerCu, kHaloBf16x3_128, "conv3x3_halo_bf16x3 (transposed)"},
+#ifdef LWG_EXPERIMENTS
+    {&conv_igemm_bf16x3<128, 2, 2, 4, 1024>, 256, ring_lds(4, 128), kIgemmBf16x3_128, "conv_igemm_bf16x3"},   // LWG_RING=x: timing only, WRONG RESULTS (see DBG & 1024)
+    {&conv_igemm_bf16x3<128, 2, 2, 5>, 256, ring_lds(5, 128), kIgemmBf16x3_128, "conv_igemm_bf16x3"},         // LWG_RING=5: all 160 KiB of a CU's LDS
+#endif
+};
 
 // the shapes conv3x3_halo_bf16x3 takes (3x3 / stride 1 / pad 1, or the four phases of ConvTranspose2d(k3, s2, p1, op1))
 static bool halo3x3_shape(const ConvArgs &a)
@@ -1864,19 +1932,44 @@ static bool haloCT_shape(const ConvArgs &a)
            a.ph[2].KH == 2 && a.ph[2].KW == 1 && a.ph[3].KH == 2 && a.ph[3].KW == 2 && a.ph[0].Kpad == a.Cin &&
            a.ph[1].Kpad == 2 * a.Cin && a.ph[2].Kpad == 2 * a.Cin && a.ph[3].Kpad == 4 * a.Cin;
 }
-bool conv_raw_input_supported(const ConvArgs &a, int bn)
+
+// A/B switches of the route, read from the environment once per process
+struct ConvSwitches {
+    bool halo, halo_tall, ct_wide, ring3, ring_tall, fused_apply;
+    char ring_exp;   // LWG_EXPERIMENTS builds: LWG_RING=x / 5
+};
+static const ConvSwitches &conv_switches()
 {
-    static const char *halo_env = getenv("LWG_HALO"), *fused_env = getenv("LWG_FUSED_APPLY");   // A/B switches ("0": off)
-    if ((halo_env && halo_env[0] == '0') || (fused_env && fused_env[0] == '0')) return false;
-    if (a.precision != 1 || a.general || !a.w_split || (a.ldx & 31) || (a.Cin & 31) || a.Cin < 32 || (bn != 64 && bn != 128)) return false;
-    if (a.raw_from < 0 || (a.raw_from & 31) || a.raw_from >= a.Cin || a.Cin - a.raw_from > 512) return false;
-    return halo3x3_shape(a) || haloCT_shape(a);
+    static const ConvSwitches sw = [] {
+        auto first = [](const char *name) { const char *v = getenv(name); return v ? v[0] : '\0'; };
+        return ConvSwitches{first("LWG_HALO") != '0',        // "0": the DMA-ring kernel everywhere
+                            first("LWG_HALO_TALL") != '0',   // "0": 4 x 32 halo tiles only
+                            first("LWG_CT_WIDE") != '0',     // "0": transposed convs on the 64-channel tile (two workgroups per CU)
+                            first("LWG_RING") == '3',        // "3": the round-2 3-slot ring on the 128-wide tile
+                            first("LWG_RING_TALL") != '0',   // "0": 128-row ring tiles only
+                            first("LWG_FUSED_APPLY") != '0', // "0": no raw-input consumers (an apply pass after every conv)
+                            first("LWG_RING")};
+    }();
+    return sw;
 }
 
-int launch_conv_igemm(const ConvArgs &a_in, int bn, hipStream_t st, int *variant)
+// does the bf16x3 path of the plan end in a halo kernel that honours a.raw_in?  (asked before the bf16x3 operand checks)
+static bool raw_input_route(const ConvArgs &a, int bn, const ConvSwitches &sw)
 {
-    ConvArgs a = a_in;   // (the halo launches attach a trace block)
-    a.trace = nullptr;   // only this function hands out trace blocks (lwg_conv_trace); never a caller's uninitialised field
+    if (!sw.halo || !sw.fused_apply) return false;
+    if (a.precision != 1 || a.general || !a.w_split || (a.ldx & 31) || (a.Cin & 31) || a.Cin < 32 || (bn != 64 && bn != 128)) return false;
+    if (a.raw_from < 0 || (a.raw_from & 31) || a.raw_from >= a.Cin || a.Cin - a.raw_from > kRawMaxChannels) return false;
+    return halo3x3_shape(a) || haloCT_shape(a);
+}
+bool conv_raw_input_supported(const ConvArgs &a, int bn) { return raw_input_route(a, bn, conv_switches()); }
+
+// What launch_conv_igemm does with (a, bn) on a device of `ncu` CUs: every refusal, then the kernel, its grid, its dynamic LDS
+// and, for the kernels that record a trace, the geometry of the record block.  Pure: no HIP call, no environment, no state.
+// `tracing`: a trace buffer is set (lwg_conv_trace) with `trace_free` bytes left.
+struct ConvLaunch { const ConvKernel *k; dim3 grid; size_t lds; int trace_waves, trace_stages; };   // 0 waves: not traceable
+
+static int plan_conv_igemm(const ConvArgs &a, int bn, int ncu, const ConvSwitches &sw, bool tracing, size_t trace_free, ConvLaunch *out)
+{
     // (32-channel tiles: the exact-fp32 DMA-fed kernel only)
     const bool bn32_ok = bn == 32 && a.precision == 0 && !a.general && a.Cin >= BK && a.zeros;
     if (a.Cout % bn != 0 || (bn != 64 && bn != 128 && !bn32_ok))
@@ -1891,253 +1984,78 @@ int launch_conv_igemm(const ConvArgs &a_in, int bn, hipStream_t st, int *variant
     if (a.dil < 1) LWG_FAIL(LWG_ERR_INVALID_ARG, "conv: dilation must be >= 1");
     if ((1 << a.cin_log2) != a.Cin || a.Cin < 4 || (a.ldx & 3))
         LWG_FAIL(LWG_ERR_UNSUPPORTED, "conv: Cin=%d must be a power of two >= 4 with a 16-byte aligned pixel stride", a.Cin);
-    for (int p = 0; p < a.nphase; ++p)
+    int max_taps = 0;
+    for (int p = 0; p < a.nphase; ++p) {
         if (a.ph[p].Kpad % BK != 0 || a.ph[p].Kpad < a.ph[p].ntaps * a.Cin)
             LWG_FAIL(LWG_ERR_UNSUPPORTED, "conv: bad padded K=%d for %d taps x %d channels", a.ph[p].Kpad, a.ph[p].ntaps, a.Cin);
+        if (a.ph[p].ntaps > max_taps) max_taps = a.ph[p].ntaps;
+    }
     if (a.precision == 1 && a.tap_inner)
         for (int p = 0; p < a.nphase; ++p)
             if (a.ph[p].Kpad != a.ph[p].ntaps * a.Cin)   // the taps-innermost walk addresses weight column tap*Cin + ci: no K padding
                 LWG_FAIL(LWG_ERR_UNSUPPORTED, "conv: taps-innermost walk needs K=%d == %d taps x %d channels", a.ph[p].Kpad,
                          a.ph[p].ntaps, a.Cin);
-    if (a.raw_in && (!a.in_ss || !conv_raw_input_supported(a, bn)))
+    if (a.raw_in && (!a.in_ss || !raw_input_route(a, bn, sw)))
         LWG_FAIL(LWG_ERR_UNSUPPORTED, "conv: raw (un-normalised) input is only taken by the halo-resident bf16x3 kernels");
-    const dim3 grid(a.mtiles, a.Cout / bn, a.fuse_phases ? 1 : a.nphase * (a.ksplit > 1 ? a.ksplit : 1));
-    const size_t lds = (size_t)2 * (BM + bn) * LDK * sizeof(float);
-    // the 128-channel tile needs 72 KiB of LDS: above the 64 KiB default, well inside gfx950's 160 KiB per CU
-    static DeviceOnce lds_opt_in;
-    if (!lds_opt_in.done()) {
-        const int l64 = 2 * (BM + 64) * LDK * (int)sizeof(float), l128 = 2 * (BM + 128) * LDK * (int)sizeof(float);
-        LWG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_igemm_f32<64, 1, 2, false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, l64));
-        LWG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_igemm_f32<64, 1, 2, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, l64));
-        LWG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_igemm_f32<128, 2, 2, false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, l128));
-        lds_opt_in.mark();
-    }
+
     const bool small_cin = a.Cin < BK;
-    if (a.general) {
-        static DeviceOnce gen_opt_in;
-        if (!gen_opt_in.done()) {
-            const int l64 = 2 * (BM + 64) * LDK * (int)sizeof(float), l128 = 2 * (BM + 128) * LDK * (int)sizeof(float);
-            LWG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_igemm_f32<64, 1, 2, false, 0, true>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, l64));
-            LWG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_igemm_f32<64, 1, 2, true, 0, true>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, l64));
-            LWG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_igemm_f32<128, 2, 2, false, 0, true>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, l128));
-            gen_opt_in.mark();
-        }
-        if (small_cin && bn != 64) LWG_FAIL(LWG_ERR_UNSUPPORTED, "conv: Cin=%d < %d is only built for the 64-channel tile", a.Cin, BK);
-        for (int p = 0; p < a.nphase; ++p)
-            if (a.ph[p].ntaps > 64) LWG_FAIL(LWG_ERR_UNSUPPORTED, "conv: more than 64 taps");
-        if (a.precision == 1) {   // plain fp32 operands, split in the kernel (conv_igemm_f32<..., X3>)
-            static DeviceOnce x3_opt_in;
-            if (!x3_opt_in.done()) {
-                const int l128 = 2 * (BM + 128) * LDK * (int)sizeof(float);
-                LWG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_igemm_f32<128, 2, 2, false, 0, true, true>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, l128));
-                x3_opt_in.mark();
-            }
-            if (small_cin) conv_igemm_f32<64, 1, 2, true, 0, true, true><<<grid, 256, lds, st>>>(a);
-            else if (bn == 64) conv_igemm_f32<64, 1, 2, false, 0, true, true><<<grid, 256, lds, st>>>(a);
-            else conv_igemm_f32<128, 2, 2, false, 0, true, true><<<grid, 256, lds, st>>>(a);
-        } else if (small_cin) {
-            conv_igemm_f32<64, 1, 2, true, 0, true><<<grid, 256, lds, st>>>(a);
-        } else if (bn == 64) {
-            conv_igemm_f32<64, 1, 2, false, 0, true><<<grid, 256, lds, st>>>(a);
-        } else {
-            conv_igemm_f32<128, 2, 2, false, 0, true><<<grid, 256, lds, st>>>(a);
-        }
-        if (variant) *variant = small_cin ? kIgemmSmallCin : (bn == 64 ? kIgemmReg64 : kIgemmReg128);
-        LWG_LAUNCH_CHECK("conv_igemm_f32 (general)");
+    const dim3 grid(a.mtiles, a.Cout / bn, a.fuse_phases ? 1 : a.nphase * (a.ksplit > 1 ? a.ksplit : 1));
+    const int tile = small_cin ? 2 : (bn == 128 ? 1 : 0);   // offset of the 64 / 128 / small-Cin row of a register-staged family
+    auto choose = [&](int id, dim3 g, size_t lds, int trace_waves = 0, int trace_stages = 0) -> int {
+        *out = ConvLaunch{&kConvKernelTable[id], g, lds, trace_waves, trace_stages};
+        if (lds > out->k->lds_cap) LWG_FAIL(LWG_ERR_STATE, "conv: %s asks for %zu bytes of LDS, opted in to %zu", out->k->label, lds, out->k->lds_cap);
         return LWG_OK;
+    };
+    if (a.general) {
+        if (small_cin && bn != 64) LWG_FAIL(LWG_ERR_UNSUPPORTED, "conv: Cin=%d < %d is only built for the 64-channel tile", a.Cin, BK);
+        if (max_taps > 64) LWG_FAIL(LWG_ERR_UNSUPPORTED, "conv: more than 64 taps");
+        return choose((a.precision == 1 ? kGenX3_64 : kGen_64) + tile, grid, reg_lds(bn));
     }
     if (a.precision == 1) {
-        // bf16x3 on split operands: DMA-fed ring of (BM + bn) 128-byte rows per stage
         if (small_cin || !a.w_split || !a.zeros || (a.ldx & 31) || (a.Cin & 31))
             LWG_FAIL(LWG_ERR_UNSUPPORTED, "conv: the bf16x3 path needs split weights and Cin, pixel stride multiples of 32");
         // lane offsets are unsigned 32-bit bytes from the image base: the zero run must sit above the whole input
         // tensor and within reach of its first image (see igemm_dma_body)
-        {
-            const char *x_end = reinterpret_cast<const char *>(a.x + (size_t)a.N * a.H * a.W * a.ldx);
-            const char *z = reinterpret_cast<const char *>(a.zeros);
-            if (z < x_end || (size_t)(z - reinterpret_cast<const char *>(a.x)) + (size_t)a.Cin * 4 > 0xffffffffull)
-                LWG_FAIL(LWG_ERR_UNSUPPORTED, "conv: the bf16x3 path needs its zero run behind the input tensor, within 4 GiB");
-            for (int p = 0; p < a.nphase; ++p)
-                if ((size_t)a.Cout * a.ph[p].Kpad * 4 > 0xffffffffull)
-                    LWG_FAIL(LWG_ERR_UNSUPPORTED, "conv: weight matrix too large for 32-bit lane offsets");
-        }
-        const size_t lds3 = (size_t)3 * (BM + bn) * BK * sizeof(float);
-        static DeviceOnce opt16;
-        if (!opt16.done()) {
-            LWG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_igemm_bf16x3<64, 1, 2>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 3 * (BM + 64) * BK * (int)sizeof(float)));
-            LWG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_igemm_bf16x3<128, 2, 2>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 3 * (BM + 128) * BK * (int)sizeof(float)));
-            opt16.mark();
-        }
+        const char *x_end = reinterpret_cast<const char *>(a.x + (size_t)a.N * a.H * a.W * a.ldx);
+        const char *z = reinterpret_cast<const char *>(a.zeros);
+        if (z < x_end || (size_t)(z - reinterpret_cast<const char *>(a.x)) + (size_t)a.Cin * 4 > 0xffffffffull)
+            LWG_FAIL(LWG_ERR_UNSUPPORTED, "conv: the bf16x3 path needs its zero run behind the input tensor, within 4 GiB");
         for (int p = 0; p < a.nphase; ++p)
-            if (a.ph[p].ntaps > 32) LWG_FAIL(LWG_ERR_UNSUPPORTED, "conv: more than 32 taps on the bf16x3 path");
-        // 3x3 / stride 1 / pad 1 with whole 128-pixel row blocks: the halo-resident kernel (conv3x3_halo_bf16x3)
-        static const char *halo_env = getenv("LWG_HALO");   // "0": the DMA-ring kernel everywhere (A/B switch)
-        if (!(halo_env && halo_env[0] == '0') && halo3x3_shape(a)) {
-            const int tc = 32;
-            static DeviceOnce halo_opt[8];
-            const size_t raw_bytes = a.raw_in ? (size_t)8 * BK * sizeof(float) + (size_t)(a.Cin - a.raw_from) * sizeof(float2) : 0;
-            auto run = [&](auto kern, int ns, int bmt, DeviceOnce &once) -> int {
-                const int hp = (bmt / tc + 2) * (tc + 2), nch = (hp + 7) / 8;
-                const size_t base = ((size_t)2 * nch * 8 * BK + (size_t)ns * bn * BK) * sizeof(float), bytes = base + raw_bytes;
-                if (!once.done()) {   // the raw-input variants size their (scale, shift) table per launch: opt in for up to 512 channels
-                    const size_t most = base + (a.raw_in ? (size_t)8 * BK * sizeof(float) + 512 * sizeof(float2) : 0);
-                    LWG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)most));
-                    once.mark();
-                }
-                const dim3 g(grid.x / (bmt / BM), grid.y, 1);
-                a.trace = trace_block(a, g.x, g.y, bmt == 256 ? 8 : 4, 9 * a.Cin / BK);
-                kern<<<g, bmt == 256 ? 512 : 256, bytes, st>>>(a);
-                return LWG_OK;
-            };
+            if ((size_t)a.Cout * a.ph[p].Kpad * 4 > 0xffffffffull)
+                LWG_FAIL(LWG_ERR_UNSUPPORTED, "conv: weight matrix too large for 32-bit lane offsets");
+        if (max_taps > 32) LWG_FAIL(LWG_ERR_UNSUPPORTED, "conv: more than 32 taps on the bf16x3 path");
+        const size_t raw_bytes = a.raw_in ? raw_lds(a.Cin - a.raw_from) : 0;
+        if (sw.halo && halo3x3_shape(a)) {
             // 8 x 32-pixel tiles with eight waves once every CU still gets one (the weight stage is shared by twice the MFMAs)
-            static const char *tall_env = getenv("LWG_HALO_TALL");   // "0": 4 x 32 tiles only (A/B switch)
-            const bool tall = bn == 128 && a.Hm % 8 == 0 && (long)(a.mtiles / 2) * (a.Cout / 128) >= device_cu_count() &&
-                              !(tall_env && tall_env[0] == '0');
             // (the 64-channel tile on eight waves of 32 x 64 -- one 110 KiB workgroup instead of two of 76 -- measured slower:
-            // 380 -> 348 TFLOP/s on skipper.2, gpurun_out/r03o)
-            int rc;
-            if (a.raw_in) {   // the input's InstanceNorm + ReLU + split folded into the halo (see HaloSched)
-                if (tall) rc = run(&conv3x3_halo_bf16x3<128, 2, 2, 4, 32, 256, 0, true>, 4, 256, halo_opt[6]);
-                else if (bn == 128) rc = run(&conv3x3_halo_bf16x3<128, 2, 2, 4, 32, 128, 0, true>, 4, 128, halo_opt[4]);
-                else rc = run(&conv3x3_halo_bf16x3<64, 1, 2, 3, 32, 128, 0, true>, 3, 128, halo_opt[5]);
-            } else if (tall) rc = run(&conv3x3_halo_bf16x3<128, 2, 2, 4, 32, 256>, 4, 256, halo_opt[2]);
-            else if (bn == 128) rc = run(&conv3x3_halo_bf16x3<128, 2, 2, 4, 32>, 4, 128, halo_opt[0]);
-            else rc = run(&conv3x3_halo_bf16x3<64, 1, 2, 3, 32>, 3, 128, halo_opt[1]);   // 52 + 24 KiB: two workgroups per CU
-            if (rc != LWG_OK) return rc;
-            if (variant) *variant = bn == 128 ? kHaloBf16x3_128 : kHaloBf16x3_64;
-            LWG_LAUNCH_CHECK("conv3x3_halo_bf16x3");
-            return LWG_OK;
+            // 380 -> 348 TFLOP/s on skipper.2)
+            const bool tall = bn == 128 && a.Hm % 8 == 0 && (long)(a.mtiles / 2) * (a.Cout / 128) >= ncu && sw.halo_tall;
+            const int bmt = tall ? 256 : BM;
+            return choose((a.raw_in ? kHaloRaw_64 : kHalo_64) + (tall ? 2 : bn == 128 ? 1 : 0), dim3(grid.x / (bmt / BM), grid.y, 1),
+                          halo_lds(halo3x3_px(bmt), bn == 128 ? 4 : 3, bn) + raw_bytes, bmt / 32, 9 * a.Cin / BK);
         }
-        // ConvTranspose2d(k3, s2, p1, op1) given as its four phases: one launch of the halo kernel (CT = 1)
-        if (!(halo_env && halo_env[0] == '0') && haloCT_shape(a)) {
-            static const char *ct_wide_env = getenv("LWG_CT_WIDE");   // "0": the 64-channel tile (two workgroups per CU) everywhere (A/B switch)
-            const bool wide = a.Cout % 128 == 0 && (long)a.mtiles * (a.Cout / 128) >= device_cu_count() &&
-                              !(ct_wide_env && ct_wide_env[0] == '0');
-            const int cbn = wide ? 128 : 64, ns = wide ? 4 : 3;
-            const int nch = ((4 + 1) * (32 + 1) + 7) / 8;
-            const size_t bytes = ((size_t)2 * nch * 8 * BK + (size_t)ns * cbn * BK) * sizeof(float) +
-                                 (a.raw_in ? (size_t)8 * BK * sizeof(float) + (size_t)(a.Cin - a.raw_from) * sizeof(float2) : 0);
-            const dim3 g(a.mtiles, a.Cout / cbn, 1);
-            a.trace = trace_block(a, g.x, g.y, 4, -(int)(9 * a.Cin / BK));   // negative stage count marks a transposed conv
-            static DeviceOnce ct_opt[4];
-            if (a.raw_in && wide) {
-                auto kern = &conv3x3_halo_bf16x3<128, 2, 2, 4, 32, 128, 1, true>;
-                if (!ct_opt[2].done()) {
-                    LWG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                    ct_opt[2].mark();
-                }
-                kern<<<g, 256, bytes, st>>>(a);
-            } else if (a.raw_in) {
-                auto kern = &conv3x3_halo_bf16x3<64, 1, 2, 3, 32, 128, 1, true>;
-                if (!ct_opt[3].done()) {
-                    LWG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                    ct_opt[3].mark();
-                }
-                kern<<<g, 256, bytes, st>>>(a);
-            } else if (wide) {
-                auto kern = &conv3x3_halo_bf16x3<128, 2, 2, 4, 32, 128, 1>;
-                if (!ct_opt[0].done()) {
-                    LWG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-                    ct_opt[0].mark();
-                }
-                kern<<<g, 256, bytes, st>>>(a);
-            } else {
-                auto kern = &conv3x3_halo_bf16x3<64, 1, 2, 3, 32, 128, 1>;
-                if (!ct_opt[1].done()) {
-                    LWG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-                    ct_opt[1].mark();
-                }
-                kern<<<g, 256, bytes, st>>>(a);
-            }
-            if (variant) *variant = wide ? kHaloBf16x3_128 : kHaloBf16x3_64;
-            LWG_LAUNCH_CHECK("conv3x3_halo_bf16x3 (transposed)");
-            return LWG_OK;
+        if (sw.halo && haloCT_shape(a)) {   // whatever bn asks for: the 128-channel tile once every CU still gets one
+            const bool wide = a.Cout % 128 == 0 && (long)a.mtiles * (a.Cout / 128) >= ncu && sw.ct_wide;
+            const int cbn = wide ? 128 : 64;
+            return choose((a.raw_in ? kHaloCTRaw_64 : kHaloCT_64) + wide, dim3(a.mtiles, a.Cout / cbn, 1),
+                          halo_lds(kHaloCTPx, wide ? 4 : 3, cbn) + raw_bytes, 4, -(int)(9 * a.Cin / BK));   // negative stage count marks a transposed conv
         }
-        static const char *ring = getenv("LWG_RING");   // "3": the round-2 3-slot ring on the 128-wide tile (A/B switch)
-        const bool ring4 = !(ring && ring[0] == '3');
-        if (g_trace.buf && bn == 128 && ring4) {
-            // measurement hook (lwg_conv_trace): the same kernel with s_memtime accounting, one record block per launch
-            const size_t need = (size_t)grid.x * grid.y * grid.z * 4 * 8 * sizeof(unsigned long long);
-            if (g_trace.used + need <= g_trace.bytes && g_trace.n < kTraceMaxLaunches) {
-                ConvArgs t = a;
-                t.trace = reinterpret_cast<unsigned long long *>(static_cast<char *>(g_trace.buf) + g_trace.used);
-                TraceLaunch &L = g_trace.launch[g_trace.n++];
-                L.offset = g_trace.used; L.gx = grid.x; L.gy = grid.y; L.gz = grid.z; L.waves = 4;
-                L.stages = a.ph[a.fuse_phases ? 0 : 0].Kpad / BK; L.cin = a.Cin; L.cout = a.Cout; L.hm = a.Hm; L.n = a.N;
-                g_trace.used += need;
-                static DeviceOnce optt;
-                if (!optt.done()) {
-                    LWG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_igemm_bf16x3<128, 2, 2, 4, 512>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (BM + 128) * BK * (int)sizeof(float)));
-                    optt.mark();
-                }
-                conv_igemm_bf16x3<128, 2, 2, 4, 512><<<grid, 256, (size_t)4 * (BM + 128) * BK * sizeof(float), st>>>(t);
-                if (variant) *variant = kIgemmBf16x3_128;
-                LWG_LAUNCH_CHECK("conv_igemm_bf16x3 (traced)");
-                return LWG_OK;
-            }
-        }
+        if (bn == 64) return choose(kRing_64, grid, ring_lds(3, 64));
+        // measurement hook (lwg_conv_trace): the 4-slot kernel with s_memtime accounting, one record block per launch; a full
+        // buffer falls back to the untraced choice
+        if (tracing && !sw.ring3 && (size_t)grid.x * grid.y * grid.z * 4 * 8 * sizeof(unsigned long long) <= trace_free)
+            return choose(kRing_128_Traced, grid, ring_lds(4, 128), 4, a.ph[0].Kpad / BK);
         // 256 x 128 tiles on eight waves (two per SIMD) where every CU still gets one: the two 128-row halves share the
         // weight stage and a workgroup's prologue / epilogue are paid once per 256 rows -- the stride-2 encoders
-        static const char *tall_ring_env = getenv("LWG_RING_TALL");   // "0": 128-row tiles only (A/B switch)
         // (a tile's rows are img * Hm*Wm + rem without a wrap: a 256-row tile must not straddle two images)
-        if (bn == 128 && !a.fuse_phases && a.nphase == 1 && (a.mtiles & 1) == 0 && (a.Hm * a.Wm) % 256 == 0 && !g_trace.buf &&
-            (long)(a.mtiles / 2) * (a.Cout / 128) >= device_cu_count() && !(tall_ring_env && tall_ring_env[0] == '0')) {
-            static DeviceOnce opt_tall;
-            const size_t lds_t = (size_t)3 * (256 + 128) * BK * sizeof(float);
-            if (!opt_tall.done()) {
-                LWG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_igemm_bf16x3<128, 2, 2, 3, 0, 256>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t));
-                opt_tall.mark();
-            }
-            conv_igemm_bf16x3<128, 2, 2, 3, 0, 256><<<dim3(grid.x / 2, grid.y, 1), 512, lds_t, st>>>(a);
-            if (variant) *variant = kIgemmBf16x3_128;
-            LWG_LAUNCH_CHECK("conv_igemm_bf16x3 (256-row tiles)");
-            return LWG_OK;
-        }
-        if (bn == 64) {
-            conv_igemm_bf16x3<64, 1, 2><<<grid, 256, lds3, st>>>(a);
-#ifdef LWG_EXPERIMENTS   // builds for profiles/r03_conv_experiments.md only (hipcc -DLWG_EXPERIMENTS): never in the shipped library
-        } else if (ring && ring[0] == 'x') {   // LWG_RING=x: timing experiment, WRONG RESULTS (see DBG & 1024)
-            static DeviceOnce optx;
-            if (!optx.done()) {
-                LWG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_igemm_bf16x3<128, 2, 2, 4, 1024>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (BM + 128) * BK * (int)sizeof(float)));
-                optx.mark();
-            }
-            conv_igemm_bf16x3<128, 2, 2, 4, 1024><<<grid, 256, (size_t)4 * (BM + 128) * BK * sizeof(float), st>>>(a);
-        } else if (ring && ring[0] == '5') {   // measurement switch: 5 slots = all 160 KiB of a CU's LDS
-            static DeviceOnce opt5;
-            if (!opt5.done()) {
-                LWG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_igemm_bf16x3<128, 2, 2, 5>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 5 * (BM + 128) * BK * (int)sizeof(float)));
-                opt5.mark();
-            }
-            conv_igemm_bf16x3<128, 2, 2, 5><<<grid, 256, (size_t)5 * (BM + 128) * BK * sizeof(float), st>>>(a);
+        if (!a.fuse_phases && a.nphase == 1 && (a.mtiles & 1) == 0 && (a.Hm * a.Wm) % 256 == 0 && !tracing &&
+            (long)(a.mtiles / 2) * (a.Cout / 128) >= ncu && sw.ring_tall)
+            return choose(kRing_128_Tall, dim3(grid.x / 2, grid.y, 1), ring_lds(3, 128, 256));
+#ifdef LWG_EXPERIMENTS
+        if (sw.ring_exp == 'x') return choose(kRing_128_X, grid, ring_lds(4, 128));
+        if (sw.ring_exp == '5') return choose(kRing_128_5, grid, ring_lds(5, 128));
 #endif
-        } else if (ring4) {
-            static DeviceOnce opt4;
-            if (!opt4.done()) {
-                LWG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_igemm_bf16x3<128, 2, 2, 4>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (BM + 128) * BK * (int)sizeof(float)));
-                opt4.mark();
-            }
-            conv_igemm_bf16x3<128, 2, 2, 4><<<grid, 256, (size_t)4 * (BM + 128) * BK * sizeof(float), st>>>(a);
-        } else {
-            conv_igemm_bf16x3<128, 2, 2><<<grid, 256, lds3, st>>>(a);
-        }
-        if (variant) *variant = bn == 64 ? kIgemmBf16x3_64 : kIgemmBf16x3_128;
-        LWG_LAUNCH_CHECK("conv_igemm_bf16x3");
-        return LWG_OK;
+        return sw.ring3 ? choose(kRing_128_3, grid, ring_lds(3, 128)) : choose(kRing_128_4, grid, ring_lds(4, 128));
     }
     if (small_cin && bn != 64) LWG_FAIL(LWG_ERR_UNSUPPORTED, "conv: Cin=%d < %d is only built for the 64-channel tile", a.Cin, BK);
     // Kernel choice (tools/igemm_bench.hip, warm clocks, TFLOP/s): the 64-channel tile runs best DMA-fed (118-122 vs
@@ -2145,112 +2063,65 @@ int launch_conv_igemm(const ConvArgs &a_in, int bn, hipStream_t st, int *variant
     // (the 96 KiB ring allows one per CU anyway: 127 vs 122) and register-staged when several rounds are queued
     // (74 KiB: two resident workgroups per CU, 130 vs 126).  Both kernels add the products of an output in the
     // same order, so the choice never changes a result bit.
-    const int ncu = device_cu_count();
-    const long nblocks = (long)grid.x * grid.y * grid.z;
-    bool few_taps = true;   // the DMA ring keeps a 32-bit tap mask per row: a 7x7 stem on 32 padded channels is register-staged
-    for (int p = 0; p < a.nphase; ++p) few_taps = few_taps && a.ph[p].ntaps <= 32;
-    const bool use_dma = !small_cin && a.zeros && few_taps && (bn <= 64 || nblocks <= ncu);
+    // (the DMA ring keeps a 32-bit tap mask per row: a 7x7 stem on 32 padded channels is register-staged)
+    const bool use_dma = !small_cin && a.zeros && max_taps <= 32 && (bn <= 64 || (long)grid.x * grid.y * grid.z <= ncu);
     if (a.fuse_phases && !use_dma) LWG_FAIL(LWG_ERR_UNSUPPORTED, "conv: fused phases need the DMA-fed kernel (Cin >= 32, 64-channel tile)");
-    if (use_dma) {
-        // DMA-fed 3-stage ring: (BM + bn) * 32 floats per stage
-        const size_t lds_dma = (size_t)3 * (BM + bn) * BK * sizeof(float);
-        static DeviceOnce dma_opt_in;
-        if (!dma_opt_in.done()) {
-            LWG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_igemm_dma_f32<64, 1, 2>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 3 * (BM + 64) * BK * (int)sizeof(float)));
-            LWG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_igemm_dma_f32<128, 2, 2>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 3 * (BM + 128) * BK * (int)sizeof(float)));
-            dma_opt_in.mark();
-        }
-        for (int p = 0; p < a.nphase; ++p)
-            if (a.ph[p].ntaps > 32) LWG_FAIL(LWG_ERR_UNSUPPORTED, "conv: more than 32 taps on the DMA path");
-        if (bn == 32) {
-            // 128 pixels x 32 channels, one 32 x 32 MFMA tile per wave: a launch of 64 of the 64-channel tiles (one source's
-            // 512 -> 512 layer on a 32 x 32 map) becomes 128 workgroups.  Same products in the same order per output: same bits.
-            static DeviceOnce dma32_opt_in;
-            if (!dma32_opt_in.done()) {
-                LWG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_igemm_dma_f32<32, 1, 1>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 3 * (BM + 32) * BK * (int)sizeof(float)));
-                dma32_opt_in.mark();
-            }
-            conv_igemm_dma_f32<32, 1, 1><<<grid, 256, lds_dma, st>>>(a);
-        } else if (bn == 64) {
-            conv_igemm_dma_f32<64, 1, 2><<<grid, 256, lds_dma, st>>>(a);
-        } else {
-            conv_igemm_dma_f32<128, 2, 2><<<grid, 256, lds_dma, st>>>(a);
-        }
-        if (variant) *variant = bn == 32 ? kIgemmDma32 : (bn == 64 ? kIgemmDma64 : kIgemmDma128);
-        LWG_LAUNCH_CHECK("conv_igemm_dma_f32");
-        return LWG_OK;
-    }
+    // 32-channel tiles: 128 pixels x 32 channels, one 32 x 32 MFMA tile per wave: a launch of 64 of the 64-channel tiles (one
+    // source's 512 -> 512 layer on a 32 x 32 map) becomes 128 workgroups.  Same products in the same order per output: same bits.
+    if (use_dma) return choose(bn == 32 ? kDma_32 : bn == 64 ? kDma_64 : kDma_128, grid, ring_lds(3, bn));
     if (bn != 64 && bn != 128) LWG_FAIL(LWG_ERR_UNSUPPORTED, "conv: the register-staged fp32 kernel has 64- and 128-channel tiles, not %d", bn);
-    if (variant) *variant = small_cin ? kIgemmSmallCin : (bn == 64 ? kIgemmReg64 : kIgemmReg128);
-    if (small_cin) {
-        conv_igemm_f32<64, 1, 2, true><<<grid, 256, lds, st>>>(a);
-    } else if (bn == 64) {
-        conv_igemm_f32<64, 1, 2, false><<<grid, 256, lds, st>>>(a);
-    } else {
-        conv_igemm_f32<128, 2, 2, false><<<grid, 256, lds, st>>>(a);
+    return choose(kF32_64 + tile, grid, reg_lds(bn));
+}
+
+int launch_conv_igemm(const ConvArgs &a_in, int bn, hipStream_t st, int *variant)
+{
+    ConvArgs a = a_in;   // (a traced launch attaches its record block)
+    a.trace = nullptr;   // only this function hands out trace blocks (lwg_conv_trace); never a caller's uninitialised field
+    ConvLaunch L;
+    const size_t trace_free = g_trace.n < kTraceMaxLaunches ? g_trace.bytes - g_trace.used : 0;
+    const int rc = plan_conv_igemm(a, bn, device_cu_count(), conv_switches(), g_trace.buf != nullptr, trace_free, &L);
+    if (rc != LWG_OK) return rc;
+    // the first conv launch on a device opts every kernel in to its LDS ceiling: no attribute call can fall into a later graph
+    // capture, whatever shapes it meets (the ceiling costs nothing: occupancy follows the bytes of each launch)
+    static DeviceOnce opted_in;
+    if (!opted_in.done()) {
+        for (const ConvKernel &k : kConvKernelTable)
+            LWG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds_cap));
+        opted_in.mark();
     }
-    LWG_LAUNCH_CHECK("conv_igemm_f32");
+    if (L.trace_waves) a.trace = trace_block(a, L.grid, L.trace_waves, L.trace_stages);
+    L.k->fn<<<L.grid, L.k->block, L.lds, st>>>(a);
+    if (variant) *variant = L.k->variant;
+    LWG_LAUNCH_CHECK(L.k->label);
     return LWG_OK;
 }
 
 #ifdef LWG_IGEMM_BENCH
-// ablation launcher for tools/igemm_bench.hip
+// ablation launcher for tools/igemm_bench.hip: any instantiation, opted in to the LDS it is launched with
+static void launch_capped(void (*kern)(ConvArgs), const ConvArgs &a, int bn, int block, size_t lds, hipStream_t st, int bmt = BM)
+{
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    kern<<<dim3(a.mtiles / (bmt / BM), a.Cout / bn, a.nphase), block, lds, st>>>(a);
+}
 template <int DBG>
 static void launch_dbg(const ConvArgs &a, int bn, hipStream_t st)
 {
-    const dim3 grid(a.mtiles, a.Cout / bn, a.nphase);
-    const size_t lds = (size_t)2 * (BM + bn) * LDK * sizeof(float);
-    if (bn == 64) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_igemm_f32<64, 1, 2, false, DBG>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        conv_igemm_f32<64, 1, 2, false, DBG><<<grid, 256, lds, st>>>(a);
-    } else {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_igemm_f32<128, 2, 2, false, DBG>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        conv_igemm_f32<128, 2, 2, false, DBG><<<grid, 256, lds, st>>>(a);
-    }
+    launch_capped(bn == 64 ? &conv_igemm_f32<64, 1, 2, false, DBG> : &conv_igemm_f32<128, 2, 2, false, DBG>, a, bn, 256, reg_lds(bn), st);
 }
-template <int DBG>
+template <int DBG, int NS = 3>
 static void launch_dma_dbg(const ConvArgs &a, int bn, hipStream_t st)
 {
-    const dim3 grid(a.mtiles, a.Cout / bn, a.nphase);
-    const size_t lds = (size_t)3 * (BM + bn) * BK * sizeof(float);
-    if (bn == 64) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_igemm_dma_f32<64, 1, 2, DBG>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        conv_igemm_dma_f32<64, 1, 2, DBG><<<grid, 256, lds, st>>>(a);
-    } else {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_igemm_dma_f32<128, 2, 2, DBG>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        conv_igemm_dma_f32<128, 2, 2, DBG><<<grid, 256, lds, st>>>(a);
-    }
+    launch_capped(bn == 64 ? &conv_igemm_dma_f32<64, 1, 2, DBG, NS> : &conv_igemm_dma_f32<128, 2, 2, DBG, NS>, a, bn, 256, ring_lds(NS, bn), st);
 }
 template <int NS, int DBG>
 static void launch_k_dbg(const ConvArgs &a, int bn, hipStream_t st)
 {
-    const dim3 grid(a.mtiles, a.Cout / bn, a.nphase);
-    const size_t lds = (size_t)NS * (BM + bn) * BK * sizeof(float);
-    if (bn == 64) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_igemm_bf16x3<64, 1, 2, NS, DBG>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        conv_igemm_bf16x3<64, 1, 2, NS, DBG><<<grid, 256, lds, st>>>(a);
-    } else {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_igemm_bf16x3<128, 2, 2, NS, DBG>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        conv_igemm_bf16x3<128, 2, 2, NS, DBG><<<grid, 256, lds, st>>>(a);
-    }
+    launch_capped(bn == 64 ? &conv_igemm_bf16x3<64, 1, 2, NS, DBG> : &conv_igemm_bf16x3<128, 2, 2, NS, DBG>, a, bn, 256, ring_lds(NS, bn), st);
 }
 template <int BN, int WM, int WN, int DBG>
 static void launch_w_dbg(const ConvArgs &a, hipStream_t st)
 {
-    const dim3 grid(a.mtiles, a.Cout / BN, a.nphase);
-    const size_t lds = (size_t)3 * (BM + BN) * BK * sizeof(float);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_igemm_bf16x3<BN, WM, WN, 3, DBG>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    conv_igemm_bf16x3<BN, WM, WN, 3, DBG><<<grid, 64 * (BM / (32 * WM)) * (BN / (32 * WN)), lds, st>>>(a);
+    launch_capped(&conv_igemm_bf16x3<BN, WM, WN, 3, DBG>, a, BN, 64 * (BM / (32 * WM)) * (BN / (32 * WN)), ring_lds(3, BN), st);
 }
 int launch_conv_igemm_dbg(const ConvArgs &a, int bn, int dbg, hipStream_t st)
 {
@@ -2259,15 +2130,10 @@ int launch_conv_igemm_dbg(const ConvArgs &a, int bn, int dbg, hipStream_t st)
         case 821: if (bn == 128) launch_w_dbg<128, 2, 1, 0>(a, st); else launch_w_dbg<64, 1, 1, 0>(a, st); break;
         case 812: if (bn == 128) launch_w_dbg<128, 1, 2, 0>(a, st); else launch_w_dbg<64, 1, 1, 0>(a, st); break;
         case 831: if (bn == 128) launch_w_dbg<128, 2, 1, 1>(a, st); else launch_w_dbg<64, 1, 1, 1>(a, st); break;   // no DMA
-        case 856: {   // 256x64 tile (bn 64 only)
+        case 856:   // 256x64 tile (bn 64 only)
             if (bn != 64 || (a.mtiles & 1) || (a.Hm * a.Wm) % 256 != 0) return LWG_ERR_INVALID_ARG;
-            const dim3 grid(a.mtiles / 2, a.Cout / 64, a.nphase);
-            const size_t lds = (size_t)3 * (256 + 64) * BK * sizeof(float);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_igemm_bf16x3<64, 2, 2, 3, 0, 256>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            conv_igemm_bf16x3<64, 2, 2, 3, 0, 256><<<grid, 256, lds, st>>>(a);
+            launch_capped(&conv_igemm_bf16x3<64, 2, 2, 3, 0, 256>, a, 64, 256, ring_lds(3, 64, 256), st, 256);
             break;
-        }
         case 300: {   // whatever launch_conv_igemm picks for the bf16x3 path (the halo kernel where it applies)
             ConvArgs b = a;
             b.precision = 1;
@@ -2296,20 +2162,7 @@ int launch_conv_igemm_dbg(const ConvArgs &a, int bn, int dbg, hipStream_t st)
         case 116: launch_dma_dbg<16>(a, bn, st); break;
         case 101: launch_dma_dbg<1>(a, bn, st); break;
         case 104: launch_dma_dbg<4>(a, bn, st); break;
-        case 140: {   // 4-slot ring (3 stages in flight)
-            const dim3 grid(a.mtiles, a.Cout / bn, a.nphase);
-            const size_t lds4 = (size_t)4 * (BM + bn) * BK * sizeof(float);
-            if (bn == 64) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_igemm_dma_f32<64, 1, 2, 0, 4>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4);
-                conv_igemm_dma_f32<64, 1, 2, 0, 4><<<grid, 256, lds4, st>>>(a);
-            } else {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_igemm_dma_f32<128, 2, 2, 0, 4>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4);
-                conv_igemm_dma_f32<128, 2, 2, 0, 4><<<grid, 256, lds4, st>>>(a);
-            }
-            break;
-        }
+        case 140: launch_dma_dbg<0, 4>(a, bn, st); break;   // 4-slot ring (3 stages in flight)
         default: return LWG_ERR_INVALID_ARG;
     }
     return LWG_OK;
@@ -2359,11 +2212,8 @@ int launch_heads(const HeadsArgs &a, hipStream_t st)
 {
     if (a.pred && !a.bg) LWG_FAIL(LWG_ERR_INVALID_ARG, "heads: pred requested without a background image");
     static DeviceOnce opt_in;
-    if (!opt_in.done()) {
-        LWG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&heads_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    HEADS_LDS));
-        opt_in.mark();
-    }
+    const int rc = opt_in_lds(reinterpret_cast<const void *>(&heads_kernel), HEADS_LDS, opt_in);
+    if (rc != LWG_OK) return rc;
     const dim3 grid(ceil_div(a.W, HT), ceil_div(a.H, HT), a.N);
     heads_kernel<<<grid, 256, HEADS_LDS, st>>>(a);
     LWG_LAUNCH_CHECK("heads_kernel");

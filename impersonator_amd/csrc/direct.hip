@@ -291,11 +291,8 @@ int launch_stem_bf16x3(const StemArgs &a, hipStream_t st, int max_workgroups)
     if (a.N < 1 || a.H < 1 || a.W < 1 || max_workgroups < 0) LWG_FAIL(LWG_ERR_INVALID_ARG, "stem: empty tensor or negative grid cap");
     if (a.W % ST_COLS || a.H % ST_ROWS) LWG_FAIL(LWG_ERR_UNSUPPORTED, "stem: %dx%d is not a multiple of the 2x128 tile", a.H, a.W);
     static DeviceOnce opt_in;
-    if (!opt_in.done()) {
-        LWG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&stem_bf16x3_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, ST_LDS));
-        opt_in.mark();
-    }
+    const int rc = opt_in_lds(reinterpret_cast<const void *>(&stem_bf16x3_kernel), ST_LDS, opt_in);
+    if (rc != LWG_OK) return rc;
     const int ncu = device_cu_count();
     const int ntiles = a.N * (a.H / ST_ROWS) * (a.W / ST_COLS);
     const int want = ceil_div(ntiles, ST_GROUPS);

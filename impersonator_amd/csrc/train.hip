@@ -1062,10 +1062,8 @@ int launch_wgrad(const float *go, int O, const float *in, int I, int N, int Hin,
         float *wout = S == 1 ? out : part;
         const unsigned grid = 8u * (unsigned)ceil_div(units * S, 8);
         auto run = [&](auto kern, DeviceOnce &once) -> int {
-            if (!once.done()) {
-                LWG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                once.mark();
-            }
+            const int rc = opt_in_lds(reinterpret_cast<const void *>(kern), lds, once);
+            if (rc != LWG_OK) return rc;
             kern<<<grid, 64 * nwaves, lds, st>>>(go, O, in, I, N, Hg, Wg, per, (int)S, wout, oihw);
             return LWG_OK;
         };
@@ -1134,11 +1132,8 @@ int launch_wgrad(const float *go, int O, const float *in, int I, int N, int Hin,
         const size_t lds16 = (size_t)4 * T * 128;
         if (T == 128) {
             static DeviceOnce opt_in16;
-            if (!opt_in16.done()) {
-                LWG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_bf16x3_kernel<128>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16));
-                opt_in16.mark();
-            }
+            const int rc = opt_in_lds(reinterpret_cast<const void *>(&wgrad_bf16x3_kernel<128>), lds16, opt_in16);
+            if (rc != LWG_OK) return rc;
             wgrad_bf16x3_kernel<128><<<grid, 256, lds16, st>>>(go, O, in, I, N, Hin, Win, Hg, Wg, stride, pad, per, wout, KWd, ntaps, oihw);
         } else {
             wgrad_bf16x3_kernel<64><<<grid, 256, lds16, st>>>(go, O, in, I, N, Hin, Win, Hg, Wg, stride, pad, per, wout, KWd, ntaps, oihw);
@@ -1149,11 +1144,8 @@ int launch_wgrad(const float *go, int O, const float *in, int I, int N, int Hin,
     const size_t lds = (size_t)4 * WG_PX * (T + 4) * sizeof(float);
     if (T == 128) {
         static DeviceOnce opt_in;
-        if (!opt_in.done()) {
-            LWG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_kernel<128>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)lds));
-            opt_in.mark();
-        }
+        const int rc = opt_in_lds(reinterpret_cast<const void *>(&wgrad_kernel<128>), lds, opt_in);
+        if (rc != LWG_OK) return rc;
         wgrad_kernel<128><<<grid, 256, lds, st>>>(go, O, in, I, N, Hin, Win, Hg, Wg, stride, pad, per, wout, KWd, ntaps, oihw);
     } else {
         wgrad_kernel<64><<<grid, 256, lds, st>>>(go, O, in, I, N, Hin, Win, Hg, Wg, stride, pad, per, wout, KWd, ntaps, oihw);
