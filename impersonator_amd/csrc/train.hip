@@ -1011,147 +1011,197 @@ __global__ __launch_bounds__(256, 4) void wgrad_rowk_c8_bf16x3_kernel(const floa
     }
 }
 
-// launcher: picks the tile, the pixel slices (split-K) and the partial buffer.  `part` must hold 32 * Cout*ntaps*Cin floats
-// (at most 32 slices); the result lands in `out`.
-int launch_wgrad(const float *go, int O, const float *in, int I, int N, int Hin, int Win, int Hg, int Wg, int stride, int pad,
-                 int KWd, int ntaps, int oihw, float *out, float *part, size_t part_floats, hipStream_t st, int precision = 0)
+// ---- weight-gradient dispatch: a pure plan (plan_wgrad), the table of the nine instantiations, a thin launcher.
+// out (O channels, Hg x Wg, gradient `go`) = conv(in (I channels, Hin x Win), stride, pad) with KW x (ntaps / KW) taps
+struct WgradShape { int O, I, N, Hin, Win, Hg, Wg, stride, pad, KW, ntaps, precision; };
+
+// the per-tap kernels' square tile: 128 when both channel counts are multiples of 128, else 64
+inline int wgrad_tile(int O, int I) { return (O % 128 == 0 && I % 128 == 0) ? 128 : 64; }
+
+enum WgradRoute { kWgradRow3, kWgradStem, kWgradPerTap };   // the three kernel signatures
+using WgradRow3Fn = decltype(&wgrad_row3_bf16x3_kernel<64, 64, 2, 2, 2, 2>);
+using WgradStemFn = decltype(&wgrad_rowk_c8_bf16x3_kernel<7>);
+using WgradPerTapFn = decltype(&wgrad_kernel<64>);
+struct WgradKernel {
+    WgradRoute route;
+    WgradPerTapFn per_tap; WgradRow3Fn row3; WgradStemFn stem;   // the one of `route`
+    int block; size_t lds_cap; const char *label;
+    const void *entry() const
+    {
+        return route == kWgradRow3 ? reinterpret_cast<const void *>(row3)
+                                   : route == kWgradStem ? reinterpret_cast<const void *>(stem) : reinterpret_cast<const void *>(per_tap);
+    }
+};
+constexpr size_t per_tap_f32_lds(int T) { return (size_t)4 * WG_PX * (T + 4) * sizeof(float); }   // two buffers x two operands, padded rows
+constexpr size_t per_tap_x3_lds(int T) { return (size_t)4 * T * 128; }                             // the same of 128-byte (hi | lo) rows
+constexpr size_t row3_lds(int TA, int TB) { return (size_t)2 * (TA + 3 * TB) * 128; }              // two buffers of dY + three shifted X tiles
+constexpr size_t kStemWgradLds = 2 * 2 * 64 * 128;
+
+enum WgradKernelId { kTapF32_64, kTapF32_128, kTapX3_64, kTapX3_128, kRow3_64_64, kRow3_64_128, kRow3_128_64, kRow3_128_128, kStem7, kWgradKernels };
+static const WgradKernel kWgradKernelTable[kWgradKernels] = {
+    {kWgradPerTap, &wgrad_kernel<64>, nullptr, nullptr, 256, per_tap_f32_lds(64), "wgrad_kernel<64>"},
+    {kWgradPerTap, &wgrad_kernel<128>, nullptr, nullptr, 256, per_tap_f32_lds(128), "wgrad_kernel<128>"},
+    {kWgradPerTap, &wgrad_bf16x3_kernel<64>, nullptr, nullptr, 256, per_tap_x3_lds(64), "wgrad_bf16x3_kernel<64>"},
+    {kWgradPerTap, &wgrad_bf16x3_kernel<128>, nullptr, nullptr, 256, per_tap_x3_lds(128), "wgrad_bf16x3_kernel<128>"},
+    // TA x TB = co x ci tile; the 128-wide ci tiles run eight waves
+    {kWgradRow3, nullptr, &wgrad_row3_bf16x3_kernel<64, 64, 2, 2, 2, 2>, nullptr, 256, row3_lds(64, 64), "wgrad_row3_bf16x3_kernel<64, 64>"},
+    {kWgradRow3, nullptr, &wgrad_row3_bf16x3_kernel<64, 128, 2, 2, 2, 4>, nullptr, 512, row3_lds(64, 128), "wgrad_row3_bf16x3_kernel<64, 128>"},
+    {kWgradRow3, nullptr, &wgrad_row3_bf16x3_kernel<128, 64, 4, 2, 2, 2>, nullptr, 256, row3_lds(128, 64), "wgrad_row3_bf16x3_kernel<128, 64>"},
+    {kWgradRow3, nullptr, &wgrad_row3_bf16x3_kernel<128, 128, 2, 2, 2, 4>, nullptr, 512, row3_lds(128, 128), "wgrad_row3_bf16x3_kernel<128, 128>"},
+    {kWgradStem, nullptr, nullptr, &wgrad_rowk_c8_bf16x3_kernel<7>, 256, kStemWgradLds, "wgrad_rowk_c8_bf16x3_kernel<7>"},
+};
+
+// A/B switches of the route, read from the environment once per process
+struct WgradSwitches {
+    bool row3;          // LWG_WGRAD_ROW3=0: the per-tap kernel everywhere
+    long row3_slices;   // LWG_WGRAD_ROW3_SLICES=n: force the slice count of the 3x3 row route where the cap allows n (measurement)
+};
+static const WgradSwitches &wgrad_switches()
 {
-    const long P = (long)N * Hg * Wg;
-    const size_t w_floats = (size_t)O * ntaps * I;
+    static const WgradSwitches sw = [] {
+        const char *row3 = getenv("LWG_WGRAD_ROW3"), *slices = getenv("LWG_WGRAD_ROW3_SLICES");
+        return WgradSwitches{!(row3 && row3[0] == '0'), slices ? atol(slices) : 0};
+    }();
+    return sw;
+}
+
+// The cheapest of the slice counts 1..cap (the first of equals).  s slices are ceil(P / s) pixels rounded up to whole
+// WG_PX-pixel steps, which may leave fewer slices `se`; cost(se, ps) prices se slices of ps pixels.
+template <class Cost>
+static void cheapest_slices(long P, long cap, Cost cost, long *S, long *per)
+{
+    decltype(cost(0L, 0L)) best = -1;
+    for (long s = 1; s <= cap; ++s) {
+        const long ps = ceil_div(ceil_div(P, s), WG_PX) * (long)WG_PX;
+        const long se = ceil_div(P, ps);
+        const auto c = cost(se, ps);
+        if (best < 0 || c < best) { best = c; *S = se; *per = ps; }
+    }
+}
+
+// What launch_wgrad does with a shape, a partial buffer of `part_floats` and a device of `ncu` CUs: every refusal, then the
+// kernel, its grid and dynamic LDS, the pixel slices (split-K: S slices of `per` pixels; S == 1 writes the result itself, S > 1
+// partials that the named reduction sums in slice order).  Pure: no HIP call, no environment, no state.  S fixes the order of
+// summation, i.e. the bits of the gradient: the cost expressions below are part of the result.
+enum WgradReduce { kReduceNone, kReduceSlices4, kReduceTapsDirect, kReduceTaps };
+struct WgradLaunch { const WgradKernel *k; dim3 grid; size_t lds; long S, per; WgradReduce reduce; };
+
+static int plan_wgrad(const WgradShape &s, size_t part_floats, int ncu, const WgradSwitches &sw, WgradLaunch *out)
+{
+    if (s.O % 64) LWG_FAIL(LWG_ERR_UNSUPPORTED, "wgrad: needs a multiple of 64 channels on the gradient side, got %d", s.O);
+    if (s.precision != 0 && s.precision != 1) LWG_FAIL(LWG_ERR_INVALID_ARG, "wgrad: precision %d is neither 0 (fp32) nor 1 (bf16x3)", s.precision);
+    const int O = s.O, I = s.I;
+    const long P = (long)s.N * s.Hg * s.Wg;
+    const size_t w_floats = (size_t)O * s.ntaps * I;
     // the bf16x3 loaders address both tensors with 32-bit element offsets
-    if (precision == 1 && ((size_t)N * Hin * Win * I >= ((size_t)1 << 32) || (size_t)P * O >= ((size_t)1 << 32)))
-        LWG_FAIL(LWG_ERR_UNSUPPORTED, "wgrad: tensors of 2^32 elements or more (%d x %d x %d x %d)", N, Hin, Win, I > O ? I : O);
-    auto reduce = [&](long S) -> int {
-        if (S > 1) {
-            if (w_floats % 4 == 0) reduce_slices4_kernel<<<ceil_div((long)(w_floats / 4), 256), 256, 0, st>>>(
-                reinterpret_cast<const float4 *>(part), (int)S, (long)(w_floats / 4), reinterpret_cast<float4 *>(out));
-            else reduce_slices_kernel<<<ceil_div((long)w_floats, 256), 256, 0, st>>>(part, (int)S, (long)w_floats, out);
-            LWG_LAUNCH_CHECK("reduce_slices_kernel");
-        }
+    if (s.precision == 1 && ((size_t)s.N * s.Hin * s.Win * I >= ((size_t)1 << 32) || (size_t)P * O >= ((size_t)1 << 32)))
+        LWG_FAIL(LWG_ERR_UNSUPPORTED, "wgrad: tensors of 2^32 elements or more (%d x %d x %d x %d)", s.N, s.Hin, s.Win, I > O ? I : O);
+    // slices: what the partial buffer holds, at most kWgradMaxSlices, at least one step each (the row routes used to round
+    // P / WG_PX down, the per-tap route up: the row routes take only P % WG_PX == 0, where the two agree)
+    long cap = (long)(part_floats / w_floats);
+    if (cap > kWgradMaxSlices) cap = kWgradMaxSlices;
+    if (cap > ceil_div(P, WG_PX)) cap = ceil_div(P, WG_PX);
+    if (cap < 1) cap = 1;
+    auto choose = [&](int id, dim3 grid, size_t lds, long S, long per, WgradReduce reduce) -> int {
+        *out = WgradLaunch{&kWgradKernelTable[id], grid, lds, S, per, S > 1 ? reduce : kReduceNone};
+        if (lds > out->k->lds_cap) LWG_FAIL(LWG_ERR_STATE, "wgrad: %s asks for %zu bytes of LDS, opted in to %zu", out->k->label, lds, out->k->lds_cap);
         return LWG_OK;
     };
-    // 3x3 / stride 1 / pad 1 on whole 32-pixel row segments: one kernel row per workgroup (wgrad_row3_bf16x3_kernel)
-    static const char *row3_env = getenv("LWG_WGRAD_ROW3");   // "0": the per-tap kernel everywhere (A/B switch)
-    if (precision == 1 && stride == 1 && pad == 1 && KWd == 3 && ntaps == 9 && Hin == Hg && Win == Wg && Wg % WG_PX == 0 &&
-        O % 64 == 0 && I % 64 == 0 && !(row3_env && row3_env[0] == '0')) {
-        static const char *s_env = getenv("LWG_WGRAD_ROW3_SLICES");  // force the slice count (measurement)
+    // the row routes: bf16x3, stride 1, 'same' padding, whole 32-pixel segments of an output row per step
+    const bool rows = s.precision == 1 && s.stride == 1 && s.Hin == s.Hg && s.Win == s.Wg && s.Wg % WG_PX == 0 && sw.row3;
+    // 3x3 / pad 1: one kernel row per workgroup (wgrad_row3_bf16x3_kernel)
+    if (rows && s.pad == 1 && s.KW == 3 && s.ntaps == 9 && I % 64 == 0) {
         const int TA = O % 128 == 0 ? 128 : 64, TB = I % 128 == 0 ? 128 : 64;
         const int nwaves = TB == 128 ? 8 : 4;
-        const size_t lds = (size_t)2 * (TA + 3 * TB) * 128;
-        const long units = (long)(O / TA) * (I / TB) * 3, slots = (long)device_cu_count() * (lds <= 80 * 1024 - 4096 ? 2 : 1);
+        const size_t lds = row3_lds(TA, TB);
+        const long units = (long)(O / TA) * (I / TB) * 3, slots = (long)ncu * (lds <= 80 * 1024 - 4096 ? 2 : 1);
         // a step is 3 x (TA x TB / 1024 / waves) x 6 MFMAs of 32 cycles per wave, the waves (and workgroups) of a SIMD
-        // share its pipe; a slice costs its partial's trip through reduce_slices
-        const double step_us = (slots / device_cu_count()) * (nwaves / 4) * 3.0 * (TA * TB / 1024 / nwaves) * 6 * 32 / 1800.0;
+        // share its pipe; a slice costs its partial's trip through the reduction
+        const double step_us = (slots / ncu) * (nwaves / 4) * 3.0 * (TA * TB / 1024 / nwaves) * 6 * 32 / 1800.0;
         const double slice_us = (double)w_floats * 4 / 5e6;
-        long cap = (long)(part_floats / w_floats);
-        if (cap > kWgradMaxSlices) cap = kWgradMaxSlices;
-        if (cap > P / WG_PX) cap = P / WG_PX;
-        if (cap < 1) cap = 1;
         long S = 1, per = P;
-        double best = -1.;
-        for (long s2 = 1; s2 <= cap; ++s2) {
-            const long ps = ceil_div(ceil_div(P, s2), WG_PX) * (long)WG_PX;
-            const long se = ceil_div(P, ps);
-            const double cost = (double)ceil_div(units * se, slots) * (ps / WG_PX + 3) * step_us + (se > 1 ? 3. + (se + 1) * slice_us : 0.);
-            if (best < 0 || cost < best) { best = cost; S = se; per = ps; }
-        }
-        if (s_env && atol(s_env) >= 1 && atol(s_env) <= cap) {
-            per = ceil_div(ceil_div(P, atol(s_env)), WG_PX) * (long)WG_PX;
+        cheapest_slices(P, cap, [&](long se, long ps) -> double {
+            return (double)ceil_div(units * se, slots) * (ps / WG_PX + 3) * step_us + (se > 1 ? 3. + (se + 1) * slice_us : 0.);
+        }, &S, &per);
+        if (sw.row3_slices >= 1 && sw.row3_slices <= cap) {
+            per = ceil_div(ceil_div(P, sw.row3_slices), WG_PX) * (long)WG_PX;
             S = ceil_div(P, per);
         }
-        float *wout = S == 1 ? out : part;
-        const unsigned grid = 8u * (unsigned)ceil_div(units * S, 8);
-        auto run = [&](auto kern, DeviceOnce &once) -> int {
-            const int rc = opt_in_lds(reinterpret_cast<const void *>(kern), lds, once);
-            if (rc != LWG_OK) return rc;
-            kern<<<grid, 64 * nwaves, lds, st>>>(go, O, in, I, N, Hg, Wg, per, (int)S, wout, oihw);
-            return LWG_OK;
-        };
-        static DeviceOnce once[4];
-        int rc;
-        if (TA == 128 && TB == 128) rc = run(&wgrad_row3_bf16x3_kernel<128, 128, 2, 2, 2, 4>, once[0]);
-        else if (TB == 128) rc = run(&wgrad_row3_bf16x3_kernel<64, 128, 2, 2, 2, 4>, once[1]);
-        else if (TA == 128) rc = run(&wgrad_row3_bf16x3_kernel<128, 64, 4, 2, 2, 2>, once[2]);
-        else rc = run(&wgrad_row3_bf16x3_kernel<64, 64, 2, 2, 2, 2>, once[3]);
-        if (rc != LWG_OK) return rc;
-        LWG_LAUNCH_CHECK("wgrad_row3_bf16x3_kernel");
-        if (S > 1) {   // small filters with many slices: a thread per element; big ones: coalesced through LDS
-            if ((long)O * I * 9 <= 512 * 1024)
-                reduce_taps_direct_kernel<<<ceil_div((long)O * I * 9, 256), 256, 0, st>>>(part, (int)S, O, I, 9, oihw, out);
-            else
-                reduce_taps_kernel<<<ceil_div((long)O * I, 64), 256, 0, st>>>(part, (int)S, O, I, 9, oihw, out);
-            LWG_LAUNCH_CHECK("reduce_taps_kernel");
-        }
-        return LWG_OK;
+        // small filters with many slices: a thread per element; big ones: coalesced through LDS
+        return choose(kRow3_64_64 + 2 * (TA == 128) + (TB == 128), dim3(8u * (unsigned)ceil_div(units * S, 8)), lds, S, per,
+                      (long)O * I * 9 <= 512 * 1024 ? kReduceTapsDirect : kReduceTaps);
     }
     // the 7x7 stem: eight input channels, one kernel row per workgroup (wgrad_rowk_c8_bf16x3_kernel)
-    if (precision == 1 && stride == 1 && KWd == 7 && ntaps == 49 && pad == 3 && I == 8 && Hin == Hg && Win == Wg && Wg % WG_PX == 0 &&
-        O % 64 == 0 && !(row3_env && row3_env[0] == '0')) {
-        const long units = (long)(O / 64) * 7, slots = (long)device_cu_count() * 4;
-        long cap = (long)(part_floats / w_floats);
-        if (cap > kWgradMaxSlices) cap = kWgradMaxSlices;
-        if (cap > P / WG_PX) cap = P / WG_PX;
-        if (cap < 1) cap = 1;
+    if (rows && s.pad == 3 && s.KW == 7 && s.ntaps == 49 && I == 8) {
+        const long units = (long)(O / 64) * 7, slots = (long)ncu * 4;
         long S = ceil_div(slots, units);   // one round of workgroups, no fewer than 8 steps each
         if (S > cap) S = cap;
         while (S > 1 && ceil_div(P, S) < 8 * WG_PX) --S;
         const long per = ceil_div(ceil_div(P, S), WG_PX) * (long)WG_PX;
         S = ceil_div(P, per);
-        float *wout = S == 1 ? out : part;
-        wgrad_rowk_c8_bf16x3_kernel<7><<<8u * (unsigned)ceil_div(units * S, 8), 256, 2 * 2 * 64 * 128, st>>>(go, O, in, N, Hg, Wg, per, (int)S,
-                                                                                                      wout, oihw);
-        LWG_LAUNCH_CHECK("wgrad_rowk_c8_bf16x3_kernel");
-        if (S > 1) {
-            reduce_taps_direct_kernel<<<ceil_div((long)O * I * 49, 256), 256, 0, st>>>(part, (int)S, O, I, 49, oihw, out);
-            LWG_LAUNCH_CHECK("reduce_taps_direct_kernel");
-        }
+        return choose(kStem7, dim3(8u * (unsigned)ceil_div(units * S, 8)), kStemWgradLds, S, per, kReduceTapsDirect);
+    }
+    // per tap.  The grid runs in rounds of `slots` resident workgroups (LDS: two 128-wide or four 64-wide ones per CU),
+    // each walking its slice in steps of WG_PX pixels: take the slice count with the fewest steps end to end (a 9-tap
+    // 512x512 layer is 144 tiles: 4 slices = 576 workgroups is two rounds of 32 steps, 3 slices one round of 43).
+    const int T = wgrad_tile(O, I);
+    const long tiles = (long)(O / T) * ceil_div(I, T) * s.ntaps, slots = (long)ncu * (T == 128 ? 2 : 4);
+    long S = 1, per = 0;
+    cheapest_slices(P, cap, [&](long se, long ps) -> long {
+        return ceil_div(tiles * se, slots) * (ps / WG_PX + 2) + (se > 1 ? se / 8 : 0);   // + prologue/epilogue, + reduce
+    }, &S, &per);
+    return choose((s.precision == 1 ? kTapX3_64 : kTapF32_64) + (T == 128), dim3(ceil_div(I, T), O / T, (unsigned)(s.ntaps * S)),
+                  s.precision == 1 ? per_tap_x3_lds(T) : per_tap_f32_lds(T), S, per, kReduceSlices4);
+}
+
+// `part` holds part_floats floats: the partials of as many slices as fit, 256 at the most (one filter's worth: no split and
+// `part` is not touched); the result lands in `out` (oihw = 1: PyTorch's (O, I, kh, kw), 0: the matrix layout (O, tap, I)).
+int launch_wgrad(const WgradShape &s, const float *go, const float *in, int oihw, float *out, float *part, size_t part_floats,
+                 hipStream_t st)
+{
+    WgradLaunch L;
+    const int rc = plan_wgrad(s, part_floats, device_cu_count(), wgrad_switches(), &L);
+    if (rc != LWG_OK) return rc;
+    // the first launch on a device opts every kernel in to its LDS ceiling: no attribute call can fall into a later graph capture
+    static DeviceOnce opted_in;
+    if (!opted_in.done()) {
+        for (const WgradKernel &k : kWgradKernelTable)
+            LWG_HIP(hipFuncSetAttribute(k.entry(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds_cap));
+        opted_in.mark();
+    }
+    float *wout = L.S == 1 ? out : part;
+    switch (L.k->route) {
+    case kWgradRow3:
+        L.k->row3<<<L.grid, L.k->block, L.lds, st>>>(go, s.O, in, s.I, s.N, s.Hg, s.Wg, L.per, (int)L.S, wout, oihw);
+        break;
+    case kWgradStem:
+        L.k->stem<<<L.grid, L.k->block, L.lds, st>>>(go, s.O, in, s.N, s.Hg, s.Wg, L.per, (int)L.S, wout, oihw);
+        break;
+    case kWgradPerTap:
+        L.k->per_tap<<<L.grid, L.k->block, L.lds, st>>>(go, s.O, in, s.I, s.N, s.Hin, s.Win, s.Hg, s.Wg, s.stride, s.pad, L.per, wout, s.KW,
+                                                      s.ntaps, oihw);
+        break;
+    }
+    LWG_LAUNCH_CHECK(L.k->label);
+    const long w_floats = (long)s.O * s.ntaps * s.I;
+    switch (L.reduce) {
+    case kReduceNone:
+        return LWG_OK;
+    case kReduceSlices4:   // (O % 64 == 0: whole float4s)
+        reduce_slices4_kernel<<<ceil_div(w_floats / 4, 256), 256, 0, st>>>(reinterpret_cast<const float4 *>(part), (int)L.S, w_floats / 4,
+                                                                           reinterpret_cast<float4 *>(out));
+        LWG_LAUNCH_CHECK("reduce_slices4_kernel");
+        return LWG_OK;
+    case kReduceTapsDirect:
+        reduce_taps_direct_kernel<<<ceil_div(w_floats, 256), 256, 0, st>>>(part, (int)L.S, s.O, s.I, s.ntaps, oihw, out);
+        LWG_LAUNCH_CHECK("reduce_taps_direct_kernel");
+        return LWG_OK;
+    case kReduceTaps:
+        reduce_taps_kernel<<<ceil_div((long)s.O * s.I, 64), 256, 0, st>>>(part, (int)L.S, s.O, s.I, s.ntaps, oihw, out);
+        LWG_LAUNCH_CHECK("reduce_taps_kernel");
         return LWG_OK;
     }
-    const int T = (O % 128 == 0 && I % 128 == 0) ? 128 : 64;
-    const long tiles = (long)(O / T) * ceil_div(I, T) * ntaps;
-    // Pixel slices (split-K).  The grid runs in rounds of `slots` resident workgroups (LDS: two 128-wide or four
-    // 64-wide ones per CU), each walking its slice in steps of WG_PX pixels: take the slice count with the fewest
-    // steps end to end (a 9-tap 512x512 layer is 144 tiles: 4 slices = 576 workgroups is two rounds of 32 steps,
-    // 3 slices one round of 43), within what the partial buffer holds.
-    const long slots = (long)device_cu_count() * (T == 128 ? 2 : 4);
-    long cap = (long)(part_floats / w_floats);
-    if (cap > kWgradMaxSlices) cap = kWgradMaxSlices;
-    if (cap > ceil_div(P, WG_PX)) cap = ceil_div(P, WG_PX);
-    if (cap < 1) cap = 1;
-    long S = 1, per = 0, best = -1;
-    for (long s = 1; s <= cap; ++s) {
-        const long ps = ceil_div(ceil_div(P, s), WG_PX) * (long)WG_PX;
-        const long se = ceil_div(P, ps);
-        const long cost = ceil_div(tiles * se, slots) * (ps / WG_PX + 2) + (se > 1 ? se / 8 : 0);   // + prologue/epilogue, + reduce
-        if (best < 0 || cost < best) { best = cost; S = se; per = ps; }
-    }
-    if (S > 1 && (size_t)S * w_floats > part_floats) LWG_FAIL(LWG_ERR_STATE, "wgrad: partial buffer too small");
-    float *wout = S == 1 ? out : part;
-    const dim3 grid(ceil_div(I, T), O / T, (unsigned)(ntaps * S));
-    if (precision == 1) {
-        const size_t lds16 = (size_t)4 * T * 128;
-        if (T == 128) {
-            static DeviceOnce opt_in16;
-            const int rc = opt_in_lds(reinterpret_cast<const void *>(&wgrad_bf16x3_kernel<128>), lds16, opt_in16);
-            if (rc != LWG_OK) return rc;
-            wgrad_bf16x3_kernel<128><<<grid, 256, lds16, st>>>(go, O, in, I, N, Hin, Win, Hg, Wg, stride, pad, per, wout, KWd, ntaps, oihw);
-        } else {
-            wgrad_bf16x3_kernel<64><<<grid, 256, lds16, st>>>(go, O, in, I, N, Hin, Win, Hg, Wg, stride, pad, per, wout, KWd, ntaps, oihw);
-        }
-        LWG_LAUNCH_CHECK("wgrad_bf16x3_kernel");
-        return reduce(S);
-    }
-    const size_t lds = (size_t)4 * WG_PX * (T + 4) * sizeof(float);
-    if (T == 128) {
-        static DeviceOnce opt_in;
-        const int rc = opt_in_lds(reinterpret_cast<const void *>(&wgrad_kernel<128>), lds, opt_in);
-        if (rc != LWG_OK) return rc;
-        wgrad_kernel<128><<<grid, 256, lds, st>>>(go, O, in, I, N, Hin, Win, Hg, Wg, stride, pad, per, wout, KWd, ntaps, oihw);
-    } else {
-        wgrad_kernel<64><<<grid, 256, lds, st>>>(go, O, in, I, N, Hin, Win, Hg, Wg, stride, pad, per, wout, KWd, ntaps, oihw);
-    }
-    LWG_LAUNCH_CHECK("wgrad_kernel");
-    return reduce(S);
+    return LWG_OK;
 }
 
 // ---- data-gradient weight matrices from the master copy W[co][kh*4+kw][ci] (run after every optimiser step).
@@ -1945,7 +1995,7 @@ int lwg_discriminator_create(lwg_discriminator **out, int input_nc, int ndf, int
     for (size_t l = 1; l < d->L.size(); ++l) d->L[l].cin_pad = d->L[l - 1].cout_pad;
 
     const size_t B = 2 * (size_t)max_batch;
-    size_t off = 0, part = 0;
+    size_t off = 0;
     int rc = LWG_OK;
     for (size_t l = 0; l < d->L.size() && rc == LWG_OK; ++l) {
         DLayer &L = d->L[l];
@@ -1965,15 +2015,13 @@ int lwg_discriminator_create(lwg_discriminator **out, int input_nc, int ndf, int
             L.sums = reinterpret_cast<float2 *>(p);
         }
         if (rc == LWG_OK && l > 0) rc = d_alloc(&L.wd, L.w_floats);
-        const size_t need = 32 * L.w_floats > (size_t)CS_SLICES * L.cout_pad ? 32 * L.w_floats : (size_t)CS_SLICES * L.cout_pad;
-        if (need > part) part = need;
     }
     d->nparams = off;
     // split-K partials: a layer never needs more than 32 slices, and only the small layers get that many
     size_t part_cap = 0;
     for (const DLayer &L : d->L) {
         const long P = (long)B * L.Ho * L.Ho;
-        const int T = (L.cout_pad % 128 == 0 && L.cin_pad % 128 == 0) ? 128 : 64;   // as launch_wgrad
+        const int T = wgrad_tile(L.cout_pad, L.cin_pad);
         const long tiles = (long)(L.cout_pad / T) * ceil_div(L.cin_pad, T) * 16;
         long S = ceil_div(512, tiles);
         if (S > 32) S = 32;
@@ -1981,7 +2029,6 @@ int lwg_discriminator_create(lwg_discriminator **out, int input_nc, int ndf, int
         const size_t need = (size_t)S * L.w_floats > (size_t)CS_SLICES * L.cout_pad ? (size_t)S * L.w_floats : (size_t)CS_SLICES * L.cout_pad;
         if (need > part_cap) part_cap = need;
     }
-    (void)part;
     d->part_floats = part_cap;
     if (rc == LWG_OK) rc = d_alloc(&d->params, off);
     if (rc == LWG_OK) rc = d_alloc(&d->grads, off);
@@ -2137,9 +2184,8 @@ int lwg_discriminator_backward_scaled(lwg_discriminator *d, const float *real_nc
         LWG_LAUNCH_CHECK("reduce_slices_kernel");
         // weight gradient
         const float *xin = l == 0 ? d->x0 : (d->L[l - 1].act ? d->L[l - 1].actv : d->L[l - 1].raw);
-        if ((rc = launch_wgrad(L.draw, L.cout_pad, xin, L.cin_pad, B, L.Hin, L.Hin, L.Ho, L.Ho, L.stride, 1, 4, 16, 0,
-                               d->grads + L.w_off, d->part, d->part_floats, st, d->precision)) != LWG_OK)
-            return rc;
+        const WgradShape ws{L.cout_pad, L.cin_pad, B, L.Hin, L.Hin, L.Ho, L.Ho, L.stride, 1, 4, 16, d->precision};
+        if ((rc = launch_wgrad(ws, L.draw, xin, 0, d->grads + L.w_off, d->part, d->part_floats, st)) != LWG_OK) return rc;
         if (l > 0 && (rc = d_conv_dgrad(d, l, B, st)) != LWG_OK) return rc;
     }
     return LWG_OK;
@@ -2374,6 +2420,14 @@ size_t operand_floats(const lwg_conv2d_desc *d, const ConvGeom &g)
     return align_up(xin > yout ? xin : yout, (size_t)32);
 }
 
+// the conv whose weight gradient lwg_conv2d_backward_weight computes: out (O channels) = conv(in (I channels), stride, pad).
+// Plain conv: in = x, out's gradient = dy.  ConvTranspose2d: the roles swap (dW[ci][co] pairs x[ci] with dy[co] taken 2i-1+kh).
+WgradShape wgrad_shape(const lwg_conv2d_desc *d, const ConvGeom &g)
+{
+    if (d->transposed) return WgradShape{d->Cin, d->Cout, d->N, g.Ho, g.Wo, d->H, d->W, 2, d->pad, d->k, d->k * d->k, d->precision};
+    return WgradShape{d->Cout, d->Cin, d->N, d->H, d->W, g.Ho, g.Wo, d->stride, d->pad, d->k, d->k * d->k, d->precision};
+}
+
 size_t zero_run_floats(const lwg_conv2d_desc *d) { return (size_t)(d->Cout > d->Cin ? d->Cout : d->Cin) + 32; }
 
 SplitWs carve_split(const lwg_conv2d_desc *d, const ConvGeom &g, void *ws)
@@ -2468,24 +2522,29 @@ int lwg_conv2d_backward_weight(const lwg_conv2d_desc *d, const float *x, const f
     if (ws_bytes < lwg_conv2d_workspace_bytes(d)) LWG_FAIL(LWG_ERR_INVALID_ARG, "conv2d_backward_weight: workspace too small");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     float *part = static_cast<float *>(ws);
-    // the conv whose weight gradient this is: out (O channels, grad `go`) = conv(in (I channels), stride, pad)
-    // plain conv: in = x, go = dy.  ConvTranspose2d: the roles swap (dW[ci][co] pairs x[ci] with dy[co] taken 2i-1+kh).
-    const float *in = d->transposed ? dy : x, *go = d->transposed ? x : dy;
-    const int I = d->transposed ? d->Cout : d->Cin, O = d->transposed ? d->Cin : d->Cout;
-    const int Hin = d->transposed ? g.Ho : d->H, Win = d->transposed ? g.Wo : d->W;
-    const int Hg = d->transposed ? d->H : g.Ho, Wg = d->transposed ? d->W : g.Wo;
-    const int stride = d->transposed ? 2 : d->stride, pad = d->pad, taps = d->k * d->k;
-    if (O % 64) LWG_FAIL(LWG_ERR_UNSUPPORTED, "conv2d_backward_weight: needs a multiple of 64 channels on the gradient side, got %d", O);
-    const long P = (long)d->N * Hg * Wg;
-    if ((rc = launch_wgrad(go, O, in, I, d->N, Hin, Win, Hg, Wg, stride, pad, d->k, taps, 1, dw, part, wgrad_part_floats(g), st, d->precision)) != LWG_OK) return rc;
+    const float *in = d->transposed ? dy : x, *go = d->transposed ? x : dy;   // (see wgrad_shape)
+    if ((rc = launch_wgrad(wgrad_shape(d, g), go, in, 1, dw, part, wgrad_part_floats(g), st)) != LWG_OK) return rc;
     if (dbias) {
         if (d->transposed) LWG_FAIL(LWG_ERR_UNSUPPORTED, "conv2d_backward_weight: bias gradient of a transposed conv");
         float *cs = part + wgrad_part_floats(g);
-        col_sum_partial_kernel<<<dim3(d->Cout / 64, CS_SLICES), 256, 0, st>>>(dy, P, d->Cout, cs);
+        col_sum_partial_kernel<<<dim3(d->Cout / 64, CS_SLICES), 256, 0, st>>>(dy, (long)d->N * g.Ho * g.Wo, d->Cout, cs);
         LWG_LAUNCH_CHECK("col_sum_partial_kernel");
         reduce_slices_kernel<<<ceil_div(d->Cout, 256), 256, 0, st>>>(cs, CS_SLICES, d->Cout, dbias);
         LWG_LAUNCH_CHECK("reduce_slices_kernel");
     }
+    return LWG_OK;
+}
+
+int lwg_wgrad_plan(const lwg_conv2d_desc *d, size_t part_floats, int cu_count, long long *info10)
+{
+    ConvGeom g;
+    int rc = conv_geom(d, &g);
+    if (rc != LWG_OK) return rc;
+    LWG_REQUIRE(info10 && cu_count >= 1, "wgrad_plan: NULL info10 or no compute units");
+    WgradLaunch L;
+    if ((rc = plan_wgrad(wgrad_shape(d, g), part_floats ? part_floats : wgrad_part_floats(g), cu_count, wgrad_switches(), &L)) != LWG_OK) return rc;
+    const long long info[10] = {L.k->route, L.k - kWgradKernelTable, L.grid.x, L.grid.y, L.grid.z, L.k->block, (long long)L.lds, L.S, L.per, L.reduce};
+    for (int i = 0; i < 10; ++i) info10[i] = info[i];
     return LWG_OK;
 }
 

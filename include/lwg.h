@@ -569,6 +569,16 @@ LWG_API int lwg_generator_profile_read(lwg_generator *g, int variant, int *launc
 LWG_API int lwg_conv_trace(void *device_buffer, size_t bytes);
 LWG_API int lwg_conv_trace_launch(int index, long long *info10);
 
+/* Diagnostic (tests/test_wgrad_plan.py; no reference counterpart): what lwg_conv2d_backward_weight launches for `d` on a
+ * device of cu_count compute units -- d is mapped to the weight-gradient shape as that entry point maps it (roles swapped
+ * for a transposed conv), with part_floats floats for split-K partials (0: what that entry point carves from its workspace;
+ * anything else as given, e.g. a discriminator's buffer).  info10: {route (0 3x3 row, 1 7x7 stem row, 2 per tap), row of the
+ * kernel table, grid x, y, z, block, dynamic LDS bytes, pixel slices S, pixels per slice, reduction behind the kernel
+ * (0 none, 1 reduce_slices4, 2 reduce_taps_direct, 3 reduce_taps)}.  The slice count fixes the order of summation, i.e. the
+ * bits of the gradient.  Honours the process's LWG_WGRAD_ROW3 / LWG_WGRAD_ROW3_SLICES; every refusal of backward_weight's
+ * dispatch is returned with its code.  No HIP call: needs no device. */
+LWG_API int lwg_wgrad_plan(const lwg_conv2d_desc *d, size_t part_floats, int cu_count, long long *info10);
+
 #ifdef __cplusplus
 }
 #endif

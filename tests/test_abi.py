@@ -97,6 +97,17 @@ def test_argument_validation_without_a_device():
     assert heads(bg=None) == INVALID and b"background" in lib.lwg_last_error()                  # pred without bg
     assert heads(nb=hws(2, 8, 27) - 1) == WORKSPACE
     assert heads(prec=0, nb=hws(2, 8, 27) - 1) == WORKSPACE
+    # lwg_conv2d_backward_weight (desc, x, dy, dw, dbias, ws, bytes, stream): NULL arguments and the dispatcher's own refusals
+    # (tests/test_wgrad_plan.py) come before any HIP call
+    from impersonator_amd.ops import _Desc
+    wgrad = lambda d, x=p, dy=p, dw=p, ws=p: lib.lwg_conv2d_backward_weight(ctypes.byref(d), x, dy, dw, None, ws, big, None)
+    d64 = _Desc(1, 32, 32, 64, 64, 3, 1, 1, 0, 1)
+    assert big >= lib.lwg_conv2d_workspace_bytes(ctypes.byref(d64)) > 0
+    for kw in (dict(x=None), dict(dy=None), dict(dw=None), dict(ws=None)):
+        assert wgrad(d64, **kw) == INVALID and b"NULL" in lib.lwg_last_error(), kw
+    assert lib.lwg_conv2d_backward_weight(None, p, p, p, None, p, big, None) == INVALID
+    assert wgrad(_Desc(1, 32, 32, 64, 32, 3, 1, 1, 0, 1)) == UNSUPPORTED and b"multiple of 64" in lib.lwg_last_error()
+    assert wgrad(_Desc(1, 32, 32, 32, 64, 3, 2, 1, 1, 0)) == UNSUPPORTED      # transposed: Cin is the gradient side
 
 
 def test_product_path_fails_loudly_without_gpu():

@@ -17,6 +17,7 @@ CASES = [
     # row segments that do not start at column 0 (W = 64: two 32-pixel steps per row) on both tiles of the kernel-row weight gradient
     ("3x3 s1 128->64 @64", 128, 64, 3, 1, 1, False, 64),
     ("3x3 s1 64->128 @64", 64, 128, 3, 1, 1, False, 64),
+    ("encoder 3x3 s2 128->256", 128, 256, 3, 2, 1, False, 16),   # the 128-wide tile of the per-tap weight gradient
 ]
 
 
@@ -30,8 +31,9 @@ def test_conv_bf16x3_route(case):
     carried to 16 significand bits, fp32 accumulation)."""
     from impersonator_amd import ops
     _, cin, cout, k, stride, pad, transposed, H = case
-    if H * H % 128:
-        H = 32        # the bf16x3 kernel wants whole 128-pixel tiles per image (else the call takes the fp32 kernel)
+    Ho = H if transposed else (H + 2 * pad - k) // stride + 1
+    if H * H % 128 or Ho * Ho % 128:
+        H = 32        # the bf16x3 kernel wants whole 128-pixel tiles per image, of x and of y (else the call takes the fp32 kernel)
     g = torch.Generator().manual_seed(9)
     N = 3
     x = torch.randn(N, cin, H, H, generator=g)

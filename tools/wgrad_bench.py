@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Times lwg_conv2d_backward_weight (precision bf16x3) on the generator's layer shapes at training batch size (development aid).
 
-    python tools/wgrad_bench.py [batch] [image_size]      env: LWG_WGRAD_ROW3=0 (per-tap kernel), LWG_WGRAD_ROW3_TA, LWG_WGRAD_ROW3_SLICES
+    python tools/wgrad_bench.py [batch] [image_size]      env: LWG_WGRAD_ROW3=0 (per-tap kernel), LWG_WGRAD_ROW3_SLICES=n (slice count of the 3x3 layers)
 """
 import os
 import sys
