@@ -30,6 +30,7 @@ SOURCES = [
     ("imgrid.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     ("smpl.hip", ["-fno-slp-vectorize"]),
     ("personalize.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
+    ("animate.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     ("conv.hip", []),
     ("direct.hip", []),
     ("heads.hip", []),

@@ -80,6 +80,10 @@ def build_synthetic_imitator(batch_size=8, seed=0, image_size=256, affine="ident
     if model == "swapper":
         part_fn, part_faces = synthetic.part_map_fn(rest, faces)
         imitator = Swapper(opt, hmr=hmr, render=render, generator=gen, part_fn=part_fn, part_faces=part_faces)
+    elif model == "animator":
+        from .models.animator import Animator
+        part_fn, part_faces = synthetic.part_map_fn(rest, faces)
+        imitator = Animator(opt, hmr=hmr, render=render, generator=gen, part_fn=part_fn, part_faces=part_faces)
     elif model == "viewer":
         imitator = Viewer(opt, hmr=hmr, render=render, generator=gen)
     else:

@@ -244,8 +244,9 @@ class Imitator(BaseModel):
         return torch.cat([cam, pose, src_shape.expand(n, -1)], dim=1)
 
     @torch.no_grad()
-    def transfer_params_by_smpl(self, tgt_smpl, cam_strategy='smooth', t=0):
-        """imitator.py:236-268 for one frame (85,) or a batch (n,85); sets self.tsf_info, returns tsf_inputs."""
+    def _posed_details(self, tgt_smpl, cam_strategy='smooth', t=0):
+        """imitator.py:236-248 for one frame (85,) or a batch (n,85): the target pose under the source's camera and shape
+        (`swap_smpl`) through the body model -> the details dict (theta, cam, pose, shape, verts, j2d, j3d)."""
         src_info = self.src_info
         if isinstance(tgt_smpl, np.ndarray):
             tgt_smpl = torch.tensor(tgt_smpl).float()
@@ -261,6 +262,13 @@ class Imitator(BaseModel):
         else:
             tsf_smpl = self.swap_smpl(src_info['cam'], src_info['shape'], tgt_smpl, cam_strategy=cam_strategy)
             tsf_info = self.hmr.get_details(tsf_smpl)
+        return tsf_info
+
+    @torch.no_grad()
+    def transfer_params_by_smpl(self, tgt_smpl, cam_strategy='smooth', t=0):
+        """imitator.py:236-268 for one frame (85,) or a batch (n,85); sets self.tsf_info, returns tsf_inputs."""
+        src_info = self.src_info
+        tsf_info = self._posed_details(tgt_smpl, cam_strategy, t)
         out = self.render.transfer(tsf_info['cam'], tsf_info['verts'], src_info['p2verts_c'], src_info['img'])
         tsf_info['fim'] = out['fim']
         tsf_info['wim'] = out['wim']
@@ -358,6 +366,9 @@ class Imitator(BaseModel):
     fuse = 4
     # entries of tsf_info with one row per frame (hmr.get_details + SMPLRenderer.transfer, imitator.py:236-268)
     PER_FRAME_KEYS = ('theta', 'cam', 'pose', 'shape', 'verts', 'j2d', 'j3d', 'fim', 'wim', 'cond', 'tsf_img', 'T')
+    # per-frame entries of tsf_info that `forward` takes as keyword arguments besides T, sliced with it (none here; a subclass
+    # whose generator pass needs a second flow names it, models/animator.py)
+    FORWARD_KEYS = ()
 
     @staticmethod
     def _adjacent_rows(chunks):
@@ -438,6 +449,7 @@ class Imitator(BaseModel):
                     tsf_inputs = self.transfer_params_by_smpl(whole, cam_strategy, t=items[0][1])
                     info, k0 = self.tsf_info, 0
                     whole_inputs, whole_T = tsf_inputs, info['T']
+                    whole_extra = {k: info[k] for k in self.FORWARD_KEYS}
                     for (_, t), n in zip(items, sizes):
                         # the per-frame entries are named, not inferred from a leading dimension
                         part = {k: (v[k0:k0 + n] if k in self.PER_FRAME_KEYS else v) for k, v in info.items()}
@@ -445,6 +457,7 @@ class Imitator(BaseModel):
                         k0 += n
                 else:
                     whole_inputs = whole_T = None
+                    whole_extra = {}
                     for chunk, t in items:
                         tsf_inputs = self.transfer_params_by_smpl(chunk, cam_strategy, t=t)
                         prepared.append((t, tsf_inputs, self.tsf_info, 0, int(tsf_inputs.shape[0])))
@@ -471,11 +484,12 @@ class Imitator(BaseModel):
                     if len(g) == 1:
                         t, tsf_inputs, info, _, _ = prepared[g[0]]
                         self.tsf_info = info
-                        preds = [self.forward(tsf_inputs, info['T'], generator=gen)]
+                        preds = [self.forward(tsf_inputs, info['T'], generator=gen, **{k: info[k] for k in self.FORWARD_KEYS})]
                     else:
                         lo, hi = prepared[g[0]][3], prepared[g[-1]][3] + prepared[g[-1]][4]
                         self.tsf_info = prepared[g[0]][2]
-                        both = self.forward(whole_inputs[lo:hi], whole_T[lo:hi], generator=gen)
+                        both = self.forward(whole_inputs[lo:hi], whole_T[lo:hi], generator=gen,
+                                            **{k: v[lo:hi] for k, v in whole_extra.items()})
                         preds = [both[prepared[j][3] - lo:prepared[j][3] - lo + prepared[j][4]] for j in g]
                     for j in g:
                         for v in [prepared[j][1]] + [x for x in prepared[j][2].values() if torch.is_tensor(x)]:

@@ -17,6 +17,9 @@ class ModelsFactory(object):
         if model_name == 'viewer':
             from .viewer import Viewer
             return Viewer(*args, **kwargs)
+        if model_name == 'animator':
+            from .animator import Animator
+            return Animator(*args, **kwargs)
         raise ValueError("Model %s is not part of the MI355X Imitator.forward path" % model_name)
 
 

@@ -276,6 +276,35 @@ class SMPLRenderer(nn.Module):
             out['tsf_inputs'] = torch.cat([out['tsf_img'], out['cond']], dim=1)
         return out
 
+    @torch.no_grad()
+    def animate_inputs(self, fim, wim, side, src_f2p, ref_f2p, src_img, ref_img, map_fn=None):
+        """The per-frame geometry of models/animator.py in one launch (lwg_animate_inputs): the driven pose's fim (bs,is,is) /
+        wim (bs,is,is,3), the per-row side bytes (nf+1), the two masked face-vertex tables (1,nf,3,2) and images (1,3,is,is).
+        Returns dict(cond, T_src, T_ref, tsf_img, tsf_inputs); with a 3-channel condition map `tsf_inputs` is an NCHW-shaped
+        view of the NHWC8 buffer the generator reads directly (as `transfer`), otherwise a plain NCHW tensor."""
+        lib = _lib.load()
+        fim, wim = self._cuda(fim, torch.int32), self._cuda(wim)
+        src_f2p, ref_f2p = self._cuda(src_f2p), self._cuda(ref_f2p)
+        src_img, ref_img = self._cuda(src_img), self._cuda(ref_img)
+        table = self.map_fn if map_fn is None else self._cuda(map_fn)
+        side = self._cuda(side, torch.uint8)
+        bs, s, dev = fim.shape[0], self.image_size, fim.device
+        nf, nc = src_f2p.shape[-3], table.shape[1]
+        if src_f2p.numel() != nf * 6 or ref_f2p.numel() != nf * 6 or src_img.numel() != 3 * s * s or ref_img.numel() != 3 * s * s:
+            raise ValueError("animate_inputs() composes ONE source and ONE reference onto a batch of target poses")
+        if side.numel() != nf + 1 or table.shape[0] != nf + 1 or tuple(fim.shape[1:]) != (s, s):
+            raise ValueError("animate_inputs(): side / map_fn need nf + 1 = %d rows, fim (bs, %d, %d)" % (nf + 1, s, s))
+        out = dict(cond=torch.empty((bs, nc, s, s), device=dev), T_src=torch.empty((bs, s, s, 2), device=dev),
+                   T_ref=torch.empty((bs, s, s, 2), device=dev), tsf_img=torch.empty((bs, 3, s, s), device=dev))
+        x0 = torch.empty((bs, s, s, 8), device=dev) if nc == 3 else None
+        x = torch.empty((bs, 3 + nc, s, s), device=dev) if nc != 3 else None
+        _lib.check(lib.lwg_animate_inputs(
+            _lib.ptr(fim), _lib.ptr(wim), bs, nf, s, _lib.ptr(table), nc, _lib.ptr(side), _lib.ptr(src_f2p), _lib.ptr(ref_f2p),
+            _lib.ptr(src_img), _lib.ptr(ref_img), int(self.align_corners), _lib.ptr(out['T_src']), _lib.ptr(out['T_ref']),
+            _lib.ptr(out['cond']), _lib.ptr(out['tsf_img']), _lib.ptr(x), _lib.ptr(x0), _lib.stream_ptr()))
+        out['tsf_inputs'] = x0.permute(0, 3, 1, 2)[:, :3 + nc] if x0 is not None else x
+        return out
+
 
 def eye_z(viewing_angle=30):
     return -(1. / math.tan(math.radians(viewing_angle)) + 1)

@@ -181,6 +181,24 @@ LWG_API int lwg_clamp(float *x, size_t n, float lo, float hi, lwg_stream_t strea
  * throughout, the library's bf16x3 arithmetic is narrower -- one probe pass in both arithmetics per weight set decides which one
  * serves it, and this is its `(a - b).abs().max()` without a framework kernel. */
 LWG_API int lwg_max_abs_diff(const float *a, const float *b, size_t n, float *out, lwg_stream_t stream);
+/* The per-frame geometry of Animator (impersonator_amd/models/animator.py: appearance transfer driven by a motion sequence) as ONE
+ * launch, one lane per pixel.  The reference's models/animator.py cannot run against its own utils/nmr.py, so the semantics are
+ * those of Swapper.swap (models/swapper.py:198-253) with the source's raster maps replaced by the driven pose's:
+ *   cond = map_fn[fim];  T_x = clamp(cal_bc_transform(x_f2p, fim, wim), -2, 2) for x in {src, ref};
+ *   tsf_img = grid_sample(ref_img, T_ref) * part_mask + grid_sample(src_img, T_src) * left_mask;  tsf_inputs = cat(tsf_img, cond).
+ * Inputs: fim (bs,is,is) int32 and wim (bs,is,is,3) as lwg_rasterize_fim_wim writes them; map_fn (nf+1,nc); side (nf+1) bytes, the
+ * background row included: bit 0 = the row's selected part channels sum to non-zero (part_mask), bit 1 = its kept channels do
+ * (left_mask) -- part = part_fn[fim], so the per-pixel channel sums of the reference are a property of the row; src_f2p / ref_f2p
+ * (nf,3,2), shared by the batch, already masked with lwg_mask_faces (ref: the kept parts' faces at -2, src: every other face);
+ * src_img / ref_img (3,is,is).  Outputs, any of which may be NULL except the two flows: T_src, T_ref (bs,is,is,2),
+ * cond (bs,nc,is,is), tsf_img (bs,3,is,is), tsf_inputs (bs,3+nc,is,is) NCHW, tsf_inputs_nhwc8 (bs,is,is,8) = [tsf_img(3), cond(3),
+ * 0, 0] per pixel (nc == 3 only; the layout lwg_generator_* consumes directly).
+ * Every output is bit-identical to the chain lwg_encode_fim, lwg_cal_bc_transform, lwg_clamp, lwg_grid_sample, lwg_swap_compose on
+ * the same inputs (same float expressions in the same order, no contraction). */
+LWG_API int lwg_animate_inputs(const int32_t *fim, const float *wim, int bs, int nf, int image_size, const float *map_fn, int nc,
+                               const unsigned char *side, const float *src_f2p, const float *ref_f2p, const float *src_img,
+                               const float *ref_img, int align_corners, float *T_src, float *T_ref, float *cond, float *tsf_img,
+                               float *tsf_inputs, float *tsf_inputs_nhwc8, lwg_stream_t stream);
 /* A batch of images as one uint8 picture: torchvision.utils.make_grid followed by save_image's conversion, which is how the
  * reference's run_view.py:76-85 writes its novel views.  x (n,3,H,W) fp32 NCHW -> out (grid_h,grid_w,3) uint8 HWC.
  *   layout: xmaps = min(nrow, n), ymaps = ceil(n / xmaps); grid_h = (H+padding)*ymaps + padding, grid_w = (W+padding)*xmaps +
