@@ -22,8 +22,11 @@ struct ConvPhase {
 // (16 significand bits, |v - hi - lo| <= 2^-17 |v|).  A run of 32 consecutive values (32 channels of a pixel / 32
 // reduction entries of a weight row) occupies the same 128 bytes it would as fp32: [hi x32 | lo x32].  Pixel strides,
 // channel-slice offsets (multiples of 32) and weight offsets are therefore identical in both formats, the async
-// global->LDS copy moves the same 16-byte chunks, and a product is evaluated as hi*hi + hi*lo + lo*hi on
-// v_mfma_f32_32x32x16_bf16 with fp32 accumulation (bf16 x bf16 is exact in fp32; only lo*lo, ~2^-18, is dropped).
+// global->LDS copy moves the same 16-byte chunks, and a product is evaluated as hi*hi + hi*lo + lo*hi on the bf16 matrix
+// cores with fp32 accumulation (bf16 x bf16 is exact in fp32; only lo*lo, ~2^-18, is dropped): v_mfma_f32_32x32x16_bf16 in
+// the ring, stem and general-mode kernels (a lane's 16-byte fragment = 8 k of a 16-k block, two blocks per run),
+// v_mfma_f32_16x16x32_bf16 in conv3x3_halo_bf16x3 (a lane's fragment = one of the four 16-byte slots of the hi or lo half:
+// the whole 32-k run in one instruction; the chip holds a higher clock on this shape, profiles/halo_mfma_shape.md).
 inline void split_bf16_groups(const float *src, size_t n, float *dst_opaque)   // host helper, n % 32 == 0
 {
     __bf16 *d = reinterpret_cast<__bf16 *>(dst_opaque);

@@ -34,6 +34,7 @@ namespace lwg {
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 #pragma clang diagnostic ignored "-Winline-asm"   // "m0 is reserved": the DMA asm below sets m0 itself before each use
 
 constexpr int BM = kConvBM;
@@ -1054,10 +1055,20 @@ __global__ __launch_bounds__(64 * (BMT / (32 * WM)) * (BN / (32 * WN))) void con
 // computes.  Per stage a CU now moves 16 KiB of weights + 26/9 KiB of halo = 19 KiB instead of 32 (64-channel tile: 11 instead
 // of 24, and its 76 KiB of LDS still let two workgroups share a CU).
 // The weight operand keeps the DMA ring of conv_igemm_bf16x3 (NS slots, NS-1 stages in flight, same fragment layout).
+//   * the MFMA is v_mfma_f32_16x16x32_bf16 (the ring kernel's is 32x32x16): same cycles per FLOP, but the chip, which runs
+//     these loops at its power limit, holds a higher clock on it (tools/mfma_peak.hip, profiles/halo_mfma_shape.md).  A
+//     32 x 32 tile of the wave is 2 x 2 MFMA tiles; lane l holds row l & 15 and k = 8 (l >> 4) + j of the whole 32-channel
+//     slice, so a stage is three products over K = 32 -- lo(A) hi(B), hi(A) lo(B), hi(A) hi(B) -- of 4 * TILES MFMAs each: the
+//     stage's schedule counts slots of two 16-cycle MFMAs.  Fragment sets: {lo(A), hi(B)} is read behind the previous stage's
+//     last MFMAs, {hi(A), lo(B)} behind this stage's first ones, one ds_read_b128 per MFMA.
 //   * LDS image of a halo pixel = its 128-byte [hi x32 | lo x32] run with the 16-byte slots XOR-swizzled by (p >> 1) & 7,
-//     p = halo pixel index: 32 consecutive pixels from ANY start read conflict-free with ds_read_b128 (rows 2k, 2k+1
-//     share a swizzle and sit 128 B = 32 banks apart); the four fragments of a row (hi/lo x two k-blocks) are the base
-//     address ^ 32 / ^ 64 / ^ 96.
+//     p = halo pixel index (rows 2k, 2k+1 share a swizzle and sit 128 B = 32 banks apart); a lane's hi fragment is slot
+//     l >> 4 of its pixel, the lo fragment the same address ^ 64.  A ds_read_b128 is served in four groups of 16 lanes that
+//     are not the MFMA's (lanes 0-3, 12-15, 20-27 form the first): a group takes 16 consecutive pixels, half of them in one
+//     slot and half in the next.  From a first pixel that is a multiple of 4 (every weight fragment: rows start at multiples
+//     of 16) that is conflict-free; from any other start every group is 2-way, so three halo fragment reads in four take 8
+//     LDS cycles instead of 4.  The 32x32x16 layout read conflict-free from any start; the LDS array has the room (16 reads
+//     per wave and 768-cycle stage) and the counters are in profiles/halo_mfma_shape.md.
 //   * the nine taps of a slice are nine stage bodies (everything tap-dependent is an immediate or one SGPR add); the
 //     weight ring slot is a run-time offset.
 //   * halo pieces (1 KiB = 8 pixels each, NHW per wave and slice, the last ones may repeat a chunk so that every wave
@@ -1112,7 +1123,7 @@ struct HaloSched {
     static constexpr int nwait(int t) { int n = issued(t); for (int d = 1; d <= NS - 3; ++d) n += lps((t + 9 - d) % 9); return n; }
 };
 
-// BMT = 256: eight waves (two per SIMD, 204 registers each) on an 8 x 32-pixel block -- the two 128-pixel halves share the
+// BMT = 256: eight waves (two per SIMD, 196 registers each, 209 with RAW) on an 8 x 32-pixel block -- the two 128-pixel halves share the
 // weight stage, so a CU moves 16 KiB of weights + 43/9 KiB of halo per TWO stages' worth of MFMAs.  For launches with at
 // least one such tile per CU (the skippers at batch 8, the trunk from batch 16).
 //
@@ -1129,8 +1140,109 @@ struct HaloCT {
     static constexpr int dx(int t) { return (t == 2 || t == 6 || t == 8) ? 1 : 0; }
 };
 
+// The halo kernel's epilogue: igemm_epilogue<WIDE, TC2 = TC> for accumulators in the C/D layout of the 16x16x32 MFMA (col =
+// lane & 15, row = 4 * (lane >> 4) + reg), a 32 x 32 block of the wave being acc[2i + h][2j + g], h, g in {0, 1}.  Same staging
+// through LDS into 16-byte channel-contiguous stores, same (mean, M2) per 4 x 32 block in the same `part0` numbering.  The tile
+// is TR rows x TC columns at image row h0, column w0, so row r of it is pixel (h0 + r / TC, w0 + r % TC): no run-time division.
+// The statistics are reduced per 32-row group first (eight values per lane in a fixed order, then lanes ^ 16 and ^ 32) and
+// combined over the groups in a fixed order: the bits do not depend on the instantiation that ran.
+template <int BN, int WM, int WN, int NWAVES, int BMT, int TC>
+__device__ __forceinline__ void halo_epilogue(const ConvArgs &a, const ConvPhase &ph, int phase, f32x4 (&acc)[2 * WM][2 * WN], float *smem,
+                                              int wave_m, int wave_n, int img, int h0, int w0, int n0, int part0, int sub_stride)
+{
+    // nothing of the epilogue stays live across the main loop: see igemm_epilogue
+    unsigned ones = ~0u;
+    asm volatile("" : "+s"(ones));
+    const int lane = (int)__builtin_amdgcn_mbcnt_hi(ones, __builtin_amdgcn_mbcnt_lo(ones, 0u));
+    const int tid = (wave_m * (BN / (32 * WN)) + wave_n) * 64 + lane;
+    const int col = lane & 15, rsel = 4 * (lane >> 4);
+    constexpr int TP = 36;                                  // staging pitch (floats)
+    float *stage = smem + (tid >> 6) * 32 * TP;              // one 32 x 32 block per wave at a time
+    const int rrow = lane >> 3, rcol = (lane & 7) * 4;       // read-back: 8 rows x 8 float4 per instruction
+#pragma unroll
+    for (int i = 0; i < WM; ++i)
+#pragma unroll
+        for (int j = 0; j < WN; ++j) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int g = 0; g < 2; ++g)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) stage[(16 * h + rsel + r) * TP + 16 * g + col] = acc[2 * i + h][2 * j + g][r];
+            // same wave wrote and reads: no barrier needed, only the LDS ordering of one wave
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int row = q * 8 + rrow;
+                const float4 v = *reinterpret_cast<const float4 *>(stage + row * TP + rcol);
+                const int trow = wave_m * 32 * WM + i * 32 + row;
+                const int hm = h0 + trow / TC, wm = w0 + trow % TC;
+                const size_t opix = ((size_t)img * a.Ho + hm * a.os + ph.oy0) * a.Wo + wm * a.os + ph.ox0;
+                *reinterpret_cast<float4 *>(a.y + opix * a.ldy + n0 + wave_n * 32 * WN + j * 32 + rcol) = v;
+            }
+        }
+    if (!a.partials) return;
+    float2 *red = reinterpret_cast<float2 *>(smem + NWAVES * 32 * TP);   // [BMT/32][BN], behind the staging blocks
+    auto lane_xor = [&](float v, int m) {
+        return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((lane ^ m) << 2, __builtin_bit_cast(int, v)));
+    };
+#pragma unroll
+    for (int i = 0; i < WM; ++i)
+#pragma unroll
+        for (int j = 0; j < WN; ++j)
+#pragma unroll
+            for (int g = 0; g < 2; ++g) {
+                float s = 0.f;
+#pragma unroll
+                for (int h = 0; h < 2; ++h)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) s += acc[2 * i + h][2 * j + g][r];
+                s += lane_xor(s, 16);
+                s += lane_xor(s, 32);
+                const float mu = s * (1.f / 32.f);
+                float q = 0.f;
+#pragma unroll
+                for (int h = 0; h < 2; ++h)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float d = acc[2 * i + h][2 * j + g][r] - mu;
+                        q += d * d;
+                    }
+                q += lane_xor(q, 16);
+                q += lane_xor(q, 32);
+                if (lane < 16) red[(wave_m * WM + i) * BN + wave_n * 32 * WN + j * 32 + 16 * g + col] = make_float2(mu, q);
+            }
+    __syncthreads();
+    // one (mean, M2) per 128 output pixels, whatever the workgroup's tile height: a 256-row tile writes two
+    if (tid < BN * (BMT / BM)) {
+        constexpr int RT = BM / 32;
+        const int sub = tid / BN, ch = tid - sub * BN;
+        float mean = 0.f;
+#pragma unroll
+        for (int w = 0; w < RT; ++w) mean += red[(sub * RT + w) * BN + ch].x;
+        mean *= 1.f / RT;
+        float m2 = 0.f;
+#pragma unroll
+        for (int w = 0; w < RT; ++w) {
+            const float2 p = red[(sub * RT + w) * BN + ch];
+            const float d = p.x - mean;
+            m2 += p.y + 32.f * d * d;
+        }
+        // `part0` is the index of the tile's first 128-row block; the following blocks sit `sub_stride` entries apart
+        a.partials[((size_t)phase * a.mtiles + (size_t)part0 + (size_t)sub * sub_stride) * a.Cout + n0 + ch] = make_float2(mean, m2);
+    }
+}
+
+// Waves per SIMD the register allocation is held to.  From two on (a budget of 256 registers) hipcc keeps the accumulators in
+// VGPRs and selects the MFMA form whose result is tied to its accumulator operand; with the four-wave workgroup's default
+// budget of 512 it selects the untied AGPR form of this four-pass MFMA, moves accumulator tiles between registers inside the
+// loop and takes a wave per SIMD from the 64-channel instantiations (profiles/halo_mfma_shape.md).  The four accumulator sets
+// of the 128-channel transposed conv (256 registers) leave no such choice; the plain 64-channel tile spills at four waves (128
+// registers) and its 76 KiB of LDS admit two workgroups per CU anyway.
+constexpr int halo_min_waves(int bn, int ct) { return ct ? (bn == 128 ? 1 : 2) : bn == 128 ? 2 : 3; }
+
 template <int BN, int WM, int WN, int NS, int TC, int BMT = BM, int CT = 0, bool RAW = false>
-__global__ __launch_bounds__(64 * (BMT / (32 * WM)) * (BN / (32 * WN))) void conv3x3_halo_bf16x3(const ConvArgs a)
+__global__ __launch_bounds__(64 * (BMT / (32 * WM)) * (BN / (32 * WN))) __attribute__((amdgpu_waves_per_eu(halo_min_waves(BN, CT))))
+void conv3x3_halo_bf16x3(const ConvArgs a)
 {
     constexpr int NPH = CT ? 4 : 1, PADL = CT ? 0 : 1;   // accumulator sets; halo rows / columns above and left of the tile
     constexpr int WAVES_N = BN / (32 * WN), WAVES_M = BMT / (32 * WM), NW = WAVES_M * WAVES_N;
@@ -1142,8 +1254,8 @@ __global__ __launch_bounds__(64 * (BMT / (32 * WM)) * (BN / (32 * WN))) void con
     constexpr int B_CH = BN / 8 / NW, BSTAGE = BN * BK, BOFF = 2 * HALO;
     static_assert(B_CH >= 1, "a weight chunk per wave");
     constexpr int TILES = WM * WN, Q = 6 * TILES, QB = Q * 3 / 4, NL = 2 * (WM + WN);
-    constexpr int RPM = (NL + (Q - QB) - 1) / (Q - QB);
-    constexpr int HT = RAW ? 6 : 7;                // taps in whose stages the halo pieces of the next slice are issued
+    constexpr int RPM = (NL + 2 * (Q - QB) - 1) / (2 * (Q - QB));   // fragment reads per MFMA behind the barrier
+    constexpr int HT = RAW ? 6 : 7;               // taps in whose stages the halo pieces of the next slice are issued
     using S = HaloSched<NHW, B_CH, Q, QB, NS, HT>;
     static_assert(S::hstart(9) == NHW && Q >= NHW / HT + 1 + B_CH, "halo pieces fit their taps, one piece per MFMA at most");
     static_assert(!RAW || (NW % 2 == 0 && S::tap_of(NHW - 1) + 3 <= 8), "RAW: chunk parity per wave, conversions end ahead of the barrier of tap 8");
@@ -1170,7 +1282,6 @@ __global__ __launch_bounds__(64 * (BMT / (32 * WM)) * (BN / (32 * WN))) void con
     const int img = __builtin_amdgcn_readfirstlane(bx / tiles_img), trem = bx - img * tiles_img;   // the divisions run on the VALU
     const int trow0 = __builtin_amdgcn_readfirstlane(trem / tiles_x);
     const int h0 = trow0 * TR, w0 = (trem - trow0 * tiles_x) * TC;
-    const int rem0 = h0 * a.Wm + w0;                         // origin pixel (the epilogue's 2-D row mapping starts here)
     const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float *)smem;
     auto uniform_ptr = [](const void *p) {
         const unsigned long long v = (unsigned long long)p;
@@ -1290,44 +1401,46 @@ __global__ __launch_bounds__(64 * (BMT / (32 * WM)) * (BN / (32 * WN))) void con
               __builtin_amdgcn_readfirstlane(wave_b + (unsigned)((slot * BSTAGE + jb * 8 * BK) * 4)));
     };
 
-    f32x16 acc[NPH][WM][WN];
+    // a 32 x 32 tile of the wave is 2 x 2 tiles of the 16x16x32 MFMA: the same 16 accumulators per lane and 32 x 32 tile
+    constexpr int WM2 = 2 * WM, WN2 = 2 * WN;
+    f32x4 acc[NPH][WM2][WN2];
 #pragma unroll
     for (int pp = 0; pp < NPH; ++pp)
 #pragma unroll
-        for (int i = 0; i < WM; ++i)
+        for (int i = 0; i < WM2; ++i)
 #pragma unroll
-            for (int j = 0; j < WN; ++j)
+            for (int j = 0; j < WN2; ++j)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) acc[pp][i][j][r] = 0.f;
+                for (int r = 0; r < 4; ++r) acc[pp][i][j][r] = 0.f;
 
-    // ---- fragment addressing
-    const int frow = lane & 31, half = lane >> 5, fsw = (frow >> 1) & 7;
-    int pl[WM];            // halo pixel of this lane's row of MFMA row tile i at tap (0,0)
+    // ---- fragment addressing: lane -> row lane & 15 of a 16-row tile, k = 8 (lane >> 4) + j.  The 16-byte slot lane >> 4 of
+    //      the row's hi half holds the lane's eight k of the whole slice; the lo fragment is the same address ^ 64
+    const int frow = lane & 15, fq = lane >> 4, fsw = (frow >> 1) & 7;
+    int pl[WM];            // halo pixel of this lane's row of the first 16-row tile of 32-row group i at tap (0,0)
 #pragma unroll
     for (int i = 0; i < WM; ++i) {
         const int m = wave_m * 32 * WM + i * 32;
         pl[i] = (m / TC) * HC + (m % TC) + frow;
     }
-    // byte address (within smem) of the hi fragment of k-block 0; ^32: hi of k-block 1, ^64 / ^96: the lo fragments
+    // byte address (within smem) of the hi fragment of the group's first 16-row tile; its second tile is the 16 pixels that
+    // follow in the same image row (TC % 32 == 0): 16 * 128 bytes on with the same swizzle (p + 16 has the bits 1..3 of p)
     auto a_addr = [&](int i, int tap, int hs) {
         const int p = pl[i] + (CT ? HaloCT::dy(tap) * HC + HaloCT::dx(tap) : (tap / 3) * HC + (tap % 3));
-        return hs * (HALO * 4) + p * 128 + ((half ^ ((p >> 1) & 7)) << 4);
+        return hs * (HALO * 4) + p * 128 + ((fq ^ ((p >> 1) & 7)) << 4);
     };
     const int b_row = (wave_n * 32 * WN + frow) * BK;
-    int fcol[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) fcol[c] = (((2 * c + half) ^ fsw) * 4);
-    struct Frags { float4 ah[WM], al[WM], bh[WN], bl[WN]; };
+    const int fcol = (fq ^ fsw) * 4;   // float offset of the hi fragment within a weight row; the lo fragment: ^ 16
+    struct Frags { float4 a[WM2], b[WN2]; };
     const char *smem_b = reinterpret_cast<const char *>(smem);
-    // fragment register idx of k-block kb, in the order the products consume them: lo(A), hi(B), hi(A), lo(B)
-    auto load_one = [&](const int (&aa)[WM], int bslot, int kb, Frags &f, int idx) {
-        const float *Bs = smem + BOFF + bslot * BSTAGE + b_row;
-        if (idx < WM) f.al[idx] = *reinterpret_cast<const float4 *>(smem_b + (aa[idx] ^ (64 + 32 * kb)));
-        else if (idx < WM + WN) f.bh[idx - WM] = *reinterpret_cast<const float4 *>(Bs + (idx - WM) * 32 * BK + fcol[kb]);
-        else if (idx < 2 * WM + WN) f.ah[idx - WM - WN] = *reinterpret_cast<const float4 *>(smem_b + (aa[idx - WM - WN] ^ (32 * kb)));
-        else f.bl[idx - 2 * WM - WN] = *reinterpret_cast<const float4 *>(Bs + (idx - 2 * WM - WN) * 32 * BK + fcol[2 + kb]);
+    // fragment register idx of the set {lo(A), hi(B)} (FIRST) or {hi(A), lo(B)}, in the order the products consume them: the A
+    // fragment of tile row 0, every B fragment, then the other A fragments
+    auto load_one = [&](const int (&aa)[WM], int bslot, bool first, Frags &f, int idx) {
+        const float *Bs = smem + BOFF + bslot * BSTAGE + b_row + (first ? fcol : fcol ^ 16);
+        const int ia = idx == 0 ? 0 : idx - WN2;
+        if (idx == 0 || idx > WN2) f.a[ia] = *reinterpret_cast<const float4 *>(smem_b + (aa[ia >> 1] ^ (first ? 64 : 0)) + (ia & 1) * 2048);
+        else f.b[idx - 1] = *reinterpret_cast<const float4 *>(Bs + (idx - 1) * 16 * BK);
     };
-    Frags fr;          // k-block-0 fragments of the stage about to run
+    Frags fr;          // {lo(A), hi(B)} of the stage about to run
     int cur_a[WM];     // A fragment base addresses of the stage about to run
 
     // One stage = tap T of channel slice `sl`, weights in ring slot `slot`.  ISSUE: the stage also issues the halo pieces
@@ -1356,8 +1469,8 @@ __global__ __launch_bounds__(64 * (BMT / (32 * WM)) * (BN / (32 * WN))) void con
         }
 #pragma unroll
         for (int q = 0; q < Q; ++q) {
-            const int kb = q / (3 * TILES), r = q % (3 * TILES);
-            const int t = r / TILES, i = (r / WN) % WM, j = r % WN;   // cross terms first, hi*hi last
+            // a slot is two 16-cycle MFMAs; the products run over the whole slice: lo(A) hi(B), hi(A) lo(B), then hi(A) hi(B)
+            const int t = q / (2 * TILES), r = q % (2 * TILES);
             if (q == QB) {
                 __builtin_amdgcn_sched_barrier(0);
                 if (ISSUE) {
@@ -1370,28 +1483,34 @@ __global__ __launch_bounds__(64 * (BMT / (32 * WM)) * (BN / (32 * WN))) void con
 #pragma unroll
                 for (int ii = 0; ii < WM; ++ii) nxt_a[ii] = a_addr(ii, TN, hs_next);
             }
-            const Frags &f = kb == 0 ? fr : f1;
-            const float4 a4 = t == 0 ? f.al[i] : f.ah[i];
-            const float4 b4 = t == 1 ? f.bl[j] : f.bh[j];
             constexpr int PP = CT ? HaloCT::phase(T) : 0;
-            acc[PP][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a4),
-                                                                    __builtin_bit_cast(bf16x8_t, b4), acc[PP][i][j], 0, 0, 0);
-            if (q < NL) {
-                load_one(cur_a, slot, 1, f1, q);
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            } else if (q >= QB && RPM * (q - QB) < NL) {
+            // one MFMA and the fragment read pinned behind it: {hi(A), lo(B)} of this stage behind its first NL MFMAs, the next
+            // stage's {lo(A), hi(B)} behind those that follow the barrier
+            auto mfma_and_read = [&](int e) {
+                const int u = 2 * r + e, i = u / WN2, j = u % WN2, g = 2 * q + e;
+                const float4 a4 = t == 0 ? fr.a[i] : f1.a[i];
+                const float4 b4 = t == 1 ? f1.b[j] : fr.b[j];
+                acc[PP][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a4),
+                                                                        __builtin_bit_cast(bf16x8_t, b4), acc[PP][i][j], 0, 0, 0);
+                if (g < NL) {
+                    load_one(cur_a, slot, false, f1, g);
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                } else if (g >= 2 * QB && RPM * (g - 2 * QB) < NL) {
 #pragma unroll
-                for (int r2 = 0; r2 < RPM; ++r2)
-                    if (RPM * (q - QB) + r2 < NL) load_one(nxt_a, slot1, 0, nx, RPM * (q - QB) + r2);
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x100, RPM, 0);
-            }
+                    for (int r2 = 0; r2 < RPM; ++r2)
+                        if (RPM * (g - 2 * QB) + r2 < NL) load_one(nxt_a, slot1, true, nx, RPM * (g - 2 * QB) + r2);
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x100, RPM, 0);
+                }
+            };
+            mfma_and_read(0);
+            if constexpr (!RAW) mfma_and_read(1);
             if constexpr (RAW) {
-                // the conversion of the pieces issued three taps ago, five steps per piece, one step behind each of the MFMAs ahead
-                // of the barrier (four steps where the stage has fewer than ten MFMAs there: the 64-channel tile)
+                // the conversion of the pieces issued three taps ago, five steps per piece, one step per slot ahead of the barrier,
+                // between the slot's two MFMAs (four steps where the stage has fewer than ten slots there: the 64-channel tile)
                 constexpr int NCONV = T >= 3 ? S::nh(T - 3) : 0, K0 = T >= 3 ? S::hstart(T - 3) : 0;
-                // ... behind the MFMAs that follow the pinned fragment reads of k-block 1 (q >= NL) where ten or more are left ahead
+                // ... in the slots from NL on (the pinned reads of {hi(A), lo(B)} end at slot NL / 2) where ten or more are left ahead
                 // of the barrier, else from the first one (the 64-channel tile)
                 constexpr int Q0 = QB - NL >= 10 ? NL : 0;
                 constexpr int NF = S::nfree(T, Q0);   // free MFMA slots
@@ -1411,6 +1530,7 @@ __global__ __launch_bounds__(64 * (BMT / (32 * WM)) * (BN / (32 * WN))) void con
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 }
+                mfma_and_read(1);   // the micro-steps ride between the slot's two MFMAs, a DMA piece behind the second
             }
             if (ISSUE) {
 #pragma unroll
@@ -1462,7 +1582,7 @@ __global__ __launch_bounds__(64 * (BMT / (32 * WM)) * (BN / (32 * WN))) void con
 #pragma unroll
     for (int ii = 0; ii < WM; ++ii) cur_a[ii] = a_addr(ii, 0, 0);
 #pragma unroll
-    for (int idx = 0; idx < NL; ++idx) load_one(cur_a, 0, 0, fr, idx);
+    for (int idx = 0; idx < NL; ++idx) load_one(cur_a, 0, true, fr, idx);
 
     using yes = std::integral_constant<bool, true>;
     using no = std::integral_constant<bool, false>;
@@ -1491,7 +1611,7 @@ __global__ __launch_bounds__(64 * (BMT / (32 * WM)) * (BN / (32 * WN))) void con
 #pragma unroll
     for (int pp = 0; pp < NPH; ++pp) {
         if (pp) __syncthreads();   // the previous phase's statistics scratch has been read
-        igemm_epilogue<BN, WM, WN, true, NW, BMT, TC>(a, a.ph[pp], pp, acc[pp], smem, tid, lane, wave_m, wave_n, img, rem0, n0, part0, tiles_x);
+        halo_epilogue<BN, WM, WN, NW, BMT, TC>(a, a.ph[pp], pp, acc[pp], smem, wave_m, wave_n, img, h0, w0, n0, part0, tiles_x);
     }
     if (a.trace && lane == 0) {   // record layout of conv_igemm_bf16x3's traced twin; no per-stage wait accounting here
         const unsigned long long tr_end = __builtin_amdgcn_s_memtime(), tr_rt1 = __builtin_amdgcn_s_memrealtime();

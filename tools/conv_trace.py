@@ -24,7 +24,9 @@ from impersonator_amd import _lib, demo  # noqa: E402
 STEPS = int(sys.argv[1]) if len(sys.argv) > 1 else 3
 OUT = sys.argv[2] if len(sys.argv) > 2 else None
 BATCH = 8
-MFMA_CYCLES_PER_STAGE = 24 * 32      # 24 v_mfma_f32_32x32x16_bf16 per wave and stage, 8 passes x 4 cycles each
+# 24 v_mfma_f32_32x32x16_bf16 per wave and stage, 8 passes x 4 cycles each (the ring kernel); the halo kernels issue 48
+# v_mfma_f32_16x16x32_bf16 of 4 passes: the same cycles
+MFMA_CYCLES_PER_STAGE = 24 * 32
 
 
 def run(lanes, lines):
@@ -101,7 +103,7 @@ def main():
              "waiting for the slowest one's data); `cycles per DMA issue` = s_memtime before to after one global_load_lds_dwordx4 "
              "(+ its s_mov m0), averaged over the first activation piece and the first weight piece of every stage (a wave issues "
              "8 per stage); the shader clock is the wave's cycle count over its 100 MHz s_memrealtime ticks.  A stage issues 24 "
-             "MFMAs of 32 cycles = %d cycles per wave at least; in an eight-wave launch two waves share a SIMD's matrix pipe, so "
+             "MFMAs of 32 cycles (halo kernels: 48 of 16) = %d cycles per wave at least; in an eight-wave launch two waves share a SIMD's matrix pipe, so "
              "%d cycles per wave-stage is its floor.  The halo kernels (conv3x3_halo_bf16x3: every row without a wait figure, "
              "`convT` rows = its transposed-conv form) record entry / loop start / loop end / exit only: their wait columns read 0.0 = "
              "not measured.  The ring kernel's traced twin always has four waves and a 4-slot ring.\n" % (MFMA_CYCLES_PER_STAGE, 2 * MFMA_CYCLES_PER_STAGE)]
