@@ -2393,6 +2393,136 @@ int relayout(const float *w, float *dst, int mode, int A, int B, int taps, long 
     return LWG_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Data gradient of the 7x7 stems (Conv2d(8, Cout, 7, 1, 3), Cout % 64 == 0): dx (N,H,W,8) from dy (N,H,W,Cout).
+//   dx[y][x][ci] = sum over (uy, ux, co) of dy[y - 3 + uy][x - 3 + ux][co] * w[co][ci][6 - uy][6 - ux]
+// i.e. a 7x7 conv of a Cout-channel tensor to 8 outputs with the flipped, transposed filter: the heads' contraction
+// shape (conv.hip, heads_kernel), and its tiling.  As a 64-output implicit GEMM it would cost 8 x its products.
+// thread = one image column x four consecutive rows of a 32x32 tile x the 8 outputs; dy is walked in chunks of 8
+// channels through an LDS halo (38x38 pixels, 48-byte pitch), the chunk's filter [tap][channel][output] sits behind it
+// and is read as wave-wide broadcasts.  Exact fp32 FMAs in a fixed order (chunk, kx, channel quad, ky, channel): no
+// atomics, bit-reproducible, the same bits whatever the descriptor's precision.
+constexpr int SD_T = 32, SD_H = SD_T + 6;   // tile edge, halo edge
+constexpr int SD_CH = 8;                    // dy channels per chunk
+constexpr int SD_PITCH = SD_CH + 4;         // floats per halo pixel: conflict-free b128 reads for lanes on adjacent columns
+constexpr int SD_W = 49 * SD_CH * 8;        // filter floats of one chunk
+constexpr int SD_LDS = (SD_H * SD_H * SD_PITCH + SD_W) * (int)sizeof(float);   // 81856 B: two workgroups per CU
+
+// wt[chunk][tap][c][o] = w[chunk * 8 + c][o][48 - tap] from w (Cout, 8, 7, 7): flipped in both axes, transposed
+__global__ __launch_bounds__(256) void stem_dgrad_filter_kernel(const float *__restrict__ w, float *__restrict__ wt, int total)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int o = i & 7, c = (i >> 3) & 7, rest = i >> 6;
+    const int tap = rest % 49, chunk = rest / 49;
+    wt[i] = w[((size_t)(chunk * SD_CH + c) * 8 + o) * 49 + (48 - tap)];
+}
+
+// ky taps KY0 .. KY0 + NKY - 1 of one (kx, channel quad) block: the filter quads are fetched up front, as the activation rows were
+extern "C++" {   // (this part of the file sits inside the extern "C" block of the entry points)
+template <int KY0, int NKY>
+__device__ __forceinline__ void stem_dgrad_taps(const float *wl, int kx, int q, const float4 (&hv)[10], float (&acc)[4][8])
+{
+    float4 wq[NKY][4][2];
+#pragma unroll
+    for (int k = 0; k < NKY; ++k) {
+        const float *wp = wl + (((KY0 + k) * 7 + kx) * SD_CH + q * 4) * 8;   // same address in every lane: broadcast reads
+#pragma unroll
+        for (int ci = 0; ci < 4; ++ci) {
+            wq[k][ci][0] = ld4(wp + ci * 8);
+            wq[k][ci][1] = ld4(wp + ci * 8 + 4);
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);   // keeps the scheduler from sinking the loads to their uses
+#pragma unroll
+    for (int k = 0; k < NKY; ++k)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float4 v = hv[r + KY0 + k];
+            const float vv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int ci = 0; ci < 4; ++ci) {   // fma chains per output (pack into v_pk_fma_f32 over output pairs)
+                const float4 w0 = wq[k][ci][0], w1 = wq[k][ci][1];
+                acc[r][0] = fmaf(vv[ci], w0.x, acc[r][0]);
+                acc[r][1] = fmaf(vv[ci], w0.y, acc[r][1]);
+                acc[r][2] = fmaf(vv[ci], w0.z, acc[r][2]);
+                acc[r][3] = fmaf(vv[ci], w0.w, acc[r][3]);
+                acc[r][4] = fmaf(vv[ci], w1.x, acc[r][4]);
+                acc[r][5] = fmaf(vv[ci], w1.y, acc[r][5]);
+                acc[r][6] = fmaf(vv[ci], w1.z, acc[r][6]);
+                acc[r][7] = fmaf(vv[ci], w1.w, acc[r][7]);
+            }
+        }
+}
+}   // extern "C++"
+
+__global__ __launch_bounds__(256) void stem_dgrad_kernel(const float *__restrict__ dy, const float *__restrict__ wt,
+                                                         float *__restrict__ dx, int H, int W, int Cout)
+{
+    extern __shared__ __attribute__((aligned(16))) float sd_halo[];
+    float *wl = sd_halo + SD_H * SD_H * SD_PITCH;
+    const int tid = threadIdx.x;
+    const int tx = tid & 31, tg = tid >> 5;
+    const int n = blockIdx.z;
+    const int y0 = blockIdx.y * SD_T, x0 = blockIdx.x * SD_T;
+    const float *dyn = dy + (size_t)n * H * W * Cout;
+
+    float acc[4][8];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int o = 0; o < 8; ++o) acc[r][o] = 0.f;
+
+    for (int chunk = 0; chunk < Cout / SD_CH; ++chunk) {
+        __syncthreads();
+        for (int i = tid; i < SD_H * SD_H * (SD_CH / 4); i += 256) {
+            const int pix = i / (SD_CH / 4), half = i % (SD_CH / 4);
+            const int hy = pix / SD_H, hx = pix - hy * SD_H;
+            const int gy = y0 - 3 + hy, gx = x0 - 3 + hx;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if ((unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W)
+                v = ld4(dyn + ((size_t)gy * W + gx) * Cout + chunk * SD_CH + half * 4);
+            *reinterpret_cast<float4 *>(sd_halo + pix * SD_PITCH + half * 4) = v;
+        }
+        for (int i = tid; i < SD_W / 4; i += 256) *reinterpret_cast<float4 *>(wl + i * 4) = ld4(wt + (size_t)chunk * SD_W + i * 4);
+        __syncthreads();
+        for (int kx = 0; kx < 7; ++kx)
+            for (int q = 0; q < SD_CH / 4; ++q) {
+                // the ten halo rows the thread's four pixels see, once for the seven ky taps
+                float4 hv[10];
+#pragma unroll
+                for (int hr = 0; hr < 10; ++hr) hv[hr] = ld4(sd_halo + ((tg * 4 + hr) * SD_H + tx + kx) * SD_PITCH + q * 4);
+                stem_dgrad_taps<0, 4>(wl, kx, q, hv, acc);
+                stem_dgrad_taps<4, 3>(wl, kx, q, hv, acc);
+            }
+    }
+    const int ox = x0 + tx;
+    if (ox >= W) return;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int oy = y0 + tg * 4 + r;
+        if (oy >= H) break;
+        float *o = dx + (((size_t)n * H + oy) * W + ox) * 8;
+        *reinterpret_cast<float4 *>(o) = make_float4(acc[r][0], acc[r][1], acc[r][2], acc[r][3]);
+        *reinterpret_cast<float4 *>(o + 4) = make_float4(acc[r][4], acc[r][5], acc[r][6], acc[r][7]);
+    }
+}
+
+// wt: Cout * 8 * 49 floats of scratch (the filter's own size: the head of the conv2d workspace)
+int launch_stem_dgrad(const float *dy, const float *w, float *dx, float *wt, int N, int H, int W, int Cout, hipStream_t st)
+{
+    if (Cout % 64 || N > 65535) LWG_FAIL(LWG_ERR_UNSUPPORTED, "stem data gradient: Cout %% 64 == 0 and N <= 65535 (Cout=%d, N=%d)", Cout, N);
+    static DeviceOnce opt_in;
+    const int rc = opt_in_lds(reinterpret_cast<const void *>(&stem_dgrad_kernel), SD_LDS, opt_in);
+    if (rc != LWG_OK) return rc;
+    const int total = Cout * 8 * 49;
+    stem_dgrad_filter_kernel<<<ceil_div(total, 256), 256, 0, st>>>(w, wt, total);
+    LWG_LAUNCH_CHECK("stem_dgrad_filter_kernel");
+    stem_dgrad_kernel<<<dim3(ceil_div(W, SD_T), ceil_div(H, SD_T), N), 256, SD_LDS, st>>>(dy, wt, dx, H, W, Cout);
+    LWG_LAUNCH_CHECK("stem_dgrad_kernel");
+    return LWG_OK;
+}
+
 }  // namespace
 
 namespace {
@@ -2400,6 +2530,7 @@ namespace {
 // column-sum scratch (+ row padding of the matrix)
 // split-K partial gradients: 32 slices always, up to 256 for small filters (the 64-channel 256x256 layers have a quarter
 // of a million pixels to slice and 36 k weights), within 32 MiB
+// (the stems' data gradient puts its flipped, transposed filter -- w_floats, + 16 bytes of alignment -- at the head: covered)
 size_t wgrad_part_floats(const ConvGeom &g)
 {
     const size_t want = (size_t)kWgradMaxSlices * g.w_floats, lim = (size_t)8 << 20;
@@ -2500,6 +2631,11 @@ int lwg_conv2d_backward_data(const lwg_conv2d_desc *d, const float *dy, const fl
     }
     if (d->stride == 1) {
         if (2 * d->pad != d->k - 1) LWG_FAIL(LWG_ERR_UNSUPPORTED, "conv2d_backward_data: stride-1 convs need 'same' padding");
+        // the 7x7 stems' few-channel gradient: its own vector-ALU kernel, exact fp32 in both precisions.  Its re-laid-out filter
+        // (w_floats) goes where the GEMM's weight matrix would: the head of the workspace, 16-byte aligned inside the slack
+        if (d->k == 7 && d->Cin == 8 && d->Cout % 64 == 0)
+            return launch_stem_dgrad(dy, w, dx, reinterpret_cast<float *>(align_up((size_t)(uintptr_t)ws, (size_t)16)), d->N, d->H, d->W,
+                                     d->Cout, st);
         // rows of k*k*Cout entries, padded to the reduction slice (the heads' data gradient: 49 x 8 = 392 -> 416)
         const int pitch = (int)align_up((size_t)d->k * d->k * d->Cout, kConvBK);
         if ((rc = relayout(w, wm, 1, d->Cout, d->Cin, d->k * d->k, (long)g.w_floats, st, pitch, split)) != LWG_OK) return rc;

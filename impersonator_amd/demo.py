@@ -14,7 +14,7 @@ def default_opt(batch_size=8, image_size=256, **over):
         image_size=image_size, tex_size=3, repeat_num=6, map_name='uv_seg', gen_name='impersonator',
         batch_size=batch_size, bg_model='ORIGINAL', bg_ks=13, ft_ks=3, only_vis=False, has_detector=False,
         front_warp=False, load_path='', load_epoch=-1, smpl_model='', hmr_model='', align_corners=False,
-        bg_replace=False, swap_part='body', uv_mapping='', part_info='',
+        bg_replace=False, swap_part='body', uv_mapping='', part_info='', post_tune=False, face_model='',
         is_train=False)
     for k, v in over.items():
         setattr(opt, k, v)
@@ -63,6 +63,7 @@ def build_synthetic_imitator(batch_size=8, seed=0, image_size=256, affine="ident
     dim = 3 + map_fn.shape[1]                       # models/imitator.py:68-70: src_dim = tsf_dim = 3 + cond_nc
     render = SMPLRenderer(image_size=image_size, faces=faces, map_fn=map_fn,
                           front_map_fn=synthetic.front_map_fn(rest, faces), has_front=True,
+                          back_map_fn=synthetic.back_map_fn(rest, faces) if getattr(opt, 'post_tune', False) else None,
                           align_corners=opt.align_corners)
     gen = ImpersonatorGenerator(bg_dim=4, src_dim=dim, tsf_dim=dim, repeat_num=opt.repeat_num, image_size=image_size,
                                 max_batch=batch_size, align_corners=opt.align_corners)

@@ -35,6 +35,7 @@ class Imitator(BaseModel):
         self.src_info = None
         self.tsf_info = None
         self.first_cam = None
+        self._tuned = 0      # post_personalize calls so far: graphs recorded before the last one are stale
 
     # ------------------------------------------------------------------ construction (imitator.py:26-74)
     def _create_networks(self, hmr, render, generator, bgnet):
@@ -48,8 +49,15 @@ class Imitator(BaseModel):
             self.bgnet = self.generator.bg_model   # imitator.py:33-34: the generator's own BGNet
         self.hmr = (hmr if hmr is not None else self._create_hmr()).cuda()
         if render is None:
+            back = None
+            if getattr(opt, 'post_tune', False):
+                # post_personalize's structure term masks the back of the head out (imitator.py:441; the reference builds the
+                # table in every renderer, utils/nmr.py:152-154)
+                from ..utils import mesh
+                back = mesh.create_mapping('back', opt.uv_mapping, front_info=opt.front_info, head_info=opt.head_info,
+                                           contain_bg=True, fill_back=False)
             render = SMPLRenderer(image_size=opt.image_size, tex_size=opt.tex_size, has_front=opt.front_warp,
-                                  fill_back=False, align_corners=getattr(opt, 'align_corners', False))
+                                  fill_back=False, back_map_fn=back, align_corners=getattr(opt, 'align_corners', False))
         self.render = render.cuda()
         self.detector = None
         if getattr(opt, 'has_detector', False):
@@ -211,6 +219,7 @@ class Imitator(BaseModel):
         # ft_mask = 1 - erode(bg, ft_ks); src_inputs = cat([img * ft_mask, cond])
         ft_erode = util.morph(bg_cond, ks=opt.ft_ks, mode='erode')
         src_inputs = self.render.mask_compose(img, ft_erode, src_info['cond'], invert=True)
+        src_info['src_inputs'] = src_inputs      # kept: post_personalize trains on it and re-encodes it with the tuned weights
         src_info['feats'] = self.generator.encode_src(src_inputs)
         src_info['p2verts_c'] = p2verts_c
         if bg_done is not None:
@@ -336,8 +345,12 @@ class Imitator(BaseModel):
             tsf_inputs = self.transfer_params_by_smpl(static_smpl, cam_strategy, t=1)
             preds = self.forward(tsf_inputs, self.tsf_info['T'])
         info = self.tsf_info
+        tuned = self._tuned
 
         def run(tgt_smpl, t=1):
+            if self._tuned != tuned:
+                raise RuntimeError("frame_graph: post_personalize changed the weights and the source features since this graph was "
+                                   "recorded; record a new one")
             tgt = torch.as_tensor(tgt_smpl, dtype=torch.float32).reshape(batch, width)
             if t == 0 and cam_strategy == 'smooth':
                 static_first.copy_(tgt[0:1, 0:3], non_blocking=True)
@@ -587,5 +600,54 @@ class Imitator(BaseModel):
 
         return self._run_batches(tgt_smpls, cam_strategy, sink)
 
-    def post_personalize(self, *args, **kwargs):
-        raise NotImplementedError("post_personalize is a fine-tuning (training) loop (imitator.py:344-472): out of scope")
+    def post_personalize(self, out_dir, data_loader, visualizer, verbose=True):
+        """imitator.py:344-472: adapts the generator to the personalised source by fine-tuning it on `data_loader`'s samples
+        (models/post_tune.py: PostTuner, meta_samples) for five epochs, then serves the tuned weights.
+
+        `data_loader`: any iterable of dicts with the reference's keys (data/dataset.py:306-322 + preds, run_imitator.py:151),
+        CPU or CUDA tensors; it is walked once per epoch.  `out_dir` is not written to (the reference does not either).
+        The `fid` term is a readout without gradient (PostTuner); it is computed when `verbose` and a Sphere20a checkpoint
+        exists at `opt.face_model`.  Returns the terms of every iteration.
+
+        Afterwards: the tuned parameters are in `self.generator` (and in every lane replica predict_batches uses -- they share
+        its Parameters, a replica that does not is loaded too), graphs recorded by `frame_graph` refuse to replay,
+        `src_info['feats']` is re-encoded from the stored source inputs, and under precision='auto' the next `personalize`
+        probes the new weights."""
+        from .post_tune import PostTuner
+        if self.src_info is None:
+            raise RuntimeError("post_personalize: personalize a source first")
+        opt = self._opt
+        face = None
+        face_model = getattr(opt, 'face_model', '')
+        if verbose and face_model and os.path.isfile(face_model):
+            from ..networks.facenet import SphereFaceLoss
+            face = SphereFaceLoss(torch.load(face_model, map_location='cpu'))
+        tuner = PostTuner(self.generator, self.src_info['bg'], self.render, front_warp=opt.front_warp, face=face)
+        history, step = [], 0
+        for epoch in range(PostTuner.EPOCHS):
+            for sample in data_loader:
+                terms = tuner.optimize(sample)
+                history.append(terms)
+                if verbose:
+                    print('epoch: %d; step: %d; ' % (epoch + 1, step) + '; '.join('%s: %.6f' % kv for kv in terms.items()))
+                if verbose and step % 5 == 0 and visualizer is not None:     # :467-468
+                    images = torch.cat([sample['images'][:, 0], sample['images'][:, 1]], dim=0)
+                    self.visualize(visualizer, input_imgs=images, tsf_imgs=tuner.fake_tsf.permute(0, 3, 1, 2),
+                                   cyc_imgs=tuner.cyc_tsf.permute(0, 3, 1, 2))
+                step += 1
+        self._serve_tuned(tuner.state_dict())
+        return history
+
+    @torch.no_grad()
+    def _serve_tuned(self, state_dict):
+        """the inference engine(s) on `state_dict`; everything derived from the old weights goes"""
+        torch.cuda.synchronize()     # lanes and side streams may still be reading the old weights
+        self.generator.load_state_dict(state_dict)
+        for _, g in (getattr(self, '_lane_cache', None) or [])[1:]:
+            if g.src_model is not self.generator.src_model:
+                g.load_state_dict(state_dict)
+        self.generator.eval()                                                # :472
+        self._tuned += 1                         # frame_graph: recorded graphs are stale
+        if self.generator.precision_policy == 'auto':
+            self.generator.precision = 'auto'                                # the probe's verdict was about the old weights
+        self.src_info['feats'] = self.generator.encode_src(self.src_info['src_inputs'])

@@ -34,6 +34,10 @@ class Swapper(Imitator):
         self.part_fn = torch.as_tensor(np.ascontiguousarray(part_fn)).float().contiguous().cuda()
         self.part_faces = [list(p) for p in part_faces]
 
+    def post_personalize(self, *args, **kwargs):
+        raise NotImplementedError("Swapper.post_personalize (swapper.py:273-476: its own loss and learning-rate schedule) is not "
+                                  "built; the Imitator's and the Viewer's is (models/post_tune.py)")
+
     @staticmethod
     def create_meshgrid(image_size):
         """utils/nmr.py:490-504: identity sampling grid (is, is, 2), x fastest."""

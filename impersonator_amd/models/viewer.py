@@ -172,8 +172,12 @@ class Viewer(Imitator):
         with torch.cuda.graph(graph, capture_error_mode="thread_local"):
             preds, _ = self._view_block(self._rigid_views(src_info['verts'], static_rt), bg)
         info, T = self.tsf_info, self.T
+        tuned = self._tuned
 
         def run(rts, ts):
+            if self._tuned != tuned:
+                raise RuntimeError("view_graph: post_personalize changed the weights and the source features since this graph was "
+                                   "recorded; record a new one")
             if batch == 1 and np.ndim(rts) == 1:
                 rts = [rts]
             if len(rts) != batch:

@@ -112,6 +112,15 @@ def front_map_fn(rest, faces):
     return tab
 
 
+def back_map_fn(rest, faces):
+    """(nf+1, 1) stand-in for `create_mapping('back', ...)` (utils/mesh.py: the head's faces that are not facial): 1 for
+    faces of the upper cap that `front_map_fn` leaves out."""
+    bary = rest[faces.astype(np.int64)].mean(1)
+    tab = np.zeros((faces.shape[0] + 1, 1), np.float32)
+    tab[:-1, 0] = ((bary[:, 1] > 0.55) & (bary[:, 2] >= 0)).astype(np.float32)
+    return tab
+
+
 def part_map_fn(rest, faces, num_parts=10):
     """Stand-in for `create_mapping('par', ...)` / `get_part_face_ids('par')` (utils/mesh.py:247-345): `num_parts`
     contiguous ring bands along the body axis, part 0 at the top (the 'head').  Returns the (nf+1, num_parts+1)

@@ -441,7 +441,13 @@ LWG_API int lwg_discriminator_adam_step(lwg_discriminator *d, float lr, float be
  * precision 0: fp32 MFMA.  precision 1 (bf16x3: operands carried as two bf16 terms, three MFMA products, fp32
  * accumulation: ~2^-16 relative per operand): forward and backward_data run the inference path's kernel wherever the
  * layer fits it -- no bias, reduction-side channels a multiple of 32, output grid per image a multiple of 128 pixels, at
- * most 32 taps -- and the fp32 kernel elsewhere; backward_weight runs its own bf16x3 kernel on every layer. */
+ * most 32 taps -- and the fp32 kernel elsewhere; backward_weight runs its own bf16x3 kernel on every layer.
+ * backward_data has one few-channel case besides: stride 1, k 7, pad 3, Cin == 8, Cout % 64 == 0 -- the data gradient of the
+ * 7x7 stems (networks/generator.py:84: dy (N,H,W,Cout), w (Cout,8,7,7) -> dx (N,H,W,8)), which a second pass fed with the
+ * first pass's image needs (models/imitator.py:384-406).  It runs a vector-ALU kernel of its own (not the implicit GEMM,
+ * which would pad the 8 outputs to 64): exact fp32 FMAs in a fixed order WHATEVER `precision` says -- precision 1 gives the
+ * same bits as precision 0 -- no atomics, bit-reproducible.  N <= 65535.  Its scratch, the flipped and transposed filter
+ * (Cin * Cout * 49 floats), is inside lwg_conv2d_workspace_bytes. */
 typedef struct lwg_conv2d_desc {
     int N, H, W, Cin, Cout, k, stride, pad, transposed;
     int precision;

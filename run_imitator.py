@@ -7,6 +7,7 @@
 
     python run_imitator.py --synthetic --hmr_model H.pth --src_path S.jpg --tgt_path DIR --output_dir OUT
                                                       (synthetic body model and generator, SMPLs estimated from the images)
+    python run_imitator.py ... --post_tune --pri_path DIR     (personalise by fine-tuning first: adaptive_personalize)
 
 When `--hmr_model` names a checkpoint of the HMR regressor (the reference's hmr_tf2pt.pth, or one saved from
 `utils.synthetic.hmr_state_dict`), the SMPL parameters of source and targets are estimated from the images as the reference
@@ -55,6 +56,25 @@ def _target_smpls(imitator, tgt_paths):
     return imitator._extract_smpls_batched(tgt_paths).cpu().numpy()
 
 
+SYNTHETIC_PRIORS = 8     # --synthetic --post_tune: seeded prior poses (there is no --pri_path folder to scan)
+
+
+def adaptive_personalize(opt, imitator, visualizer=None):
+    """run_imitator.py:199-211: personalisation by fine-tuning.  The source is personalised already; the priors -- every 40th
+    file of --pri_path (meta_imitate, :72), 8 seeded poses under --synthetic -- are imitated, the samples built on the device
+    (models/post_tune.py: meta_samples; no pickles, no JPEGs) and the generator tuned on them (Imitator.post_personalize).
+    The caller personalises again afterwards, as the reference does (:229)."""
+    from impersonator_amd.models.post_tune import meta_samples
+    print('\n\t\t\tPersonalization: meta imitation...')
+    if opt.synthetic:
+        samples = meta_samples(imitator, tgt_smpls=demo.synthetic_smpls(SYNTHETIC_PRIORS, seed=7), cam_strategy=opt.cam_strategy)
+    else:
+        pri_paths = scan_tgt_paths(opt.pri_path, itv=40)
+        samples = meta_samples(imitator, tgt_paths=pri_paths, tgt_smpls=_target_smpls(imitator, pri_paths), cam_strategy=opt.cam_strategy)
+    print('\n\t\t\tPersonalization: meta cycle finetune...')
+    return imitator.post_personalize(opt.output_dir, samples, visualizer=visualizer, verbose=False)
+
+
 def main():
     opt = TestOptions().parse()
     rank, local_rank, world = sharding.init_process_group()
@@ -66,14 +86,17 @@ def main():
             batch_size=opt.batch_size, image_size=opt.image_size,
             opt=demo.default_opt(batch_size=opt.batch_size, image_size=opt.image_size, front_warp=opt.front_warp,
                                  only_vis=opt.only_vis, align_corners=opt.align_corners,
-                                 map_name=getattr(opt, 'map_name', 'uv_seg'), hmr_model=opt.hmr_model))
+                                 map_name=getattr(opt, 'map_name', 'uv_seg'), hmr_model=opt.hmr_model,
+                                 post_tune=opt.post_tune, face_model=opt.face_model))
         if hasattr(imitator.hmr, 'regressor') and opt.src_path:
             # pictures in, pictures out: SMPLs of the source and of the targets come from the HMR regressor
-            imitator.personalize(opt.src_path, bg_img=bg_img)
+            personalize = lambda: imitator.personalize(opt.src_path, bg_img=bg_img)
+            personalize()
             tgt_paths = scan_tgt_paths(opt.tgt_path, itv=1) if opt.tgt_path else None
             tgt_smpls = _target_smpls(imitator, tgt_paths) if tgt_paths else demo.synthetic_smpls(opt.num_frames, seed=0)
         else:
-            imitator.personalize(src_img, src_smpl=src_smpl, bg_img=bg_img)
+            personalize = lambda: imitator.personalize(src_img, src_smpl=src_smpl, bg_img=bg_img)
+            personalize()
             tgt_smpls = demo.synthetic_smpls(opt.num_frames, seed=0)
             tgt_paths = None
     else:
@@ -84,9 +107,14 @@ def main():
         if os.path.exists(bg_file):
             bg = np.load(bg_file)
         have_hmr = hasattr(imitator.hmr, 'regressor')
-        imitator.personalize(opt.src_path, src_smpl=_smpl_of(opt.src_path, optional=have_hmr), bg_img=bg)
+        personalize = lambda: imitator.personalize(opt.src_path, src_smpl=_smpl_of(opt.src_path, optional=have_hmr), bg_img=bg)
+        personalize()
         tgt_paths = scan_tgt_paths(opt.tgt_path, itv=1)
         tgt_smpls = _target_smpls(imitator, tgt_paths)
+    if opt.post_tune:
+        adaptive_personalize(opt, imitator, None)
+        personalize()            # run_imitator.py:229: once more, on the tuned weights
+        print('\n\t\t\tPersonalization: completed...')
 
     # frame sharding: every rank imitates its own blocks of `batch_size` frames (first_cam = frame 0's camera everywhere)
     outs = sharding.imitate_sharded(imitator, tgt_smpls, opt.batch_size, opt.cam_strategy, rank, world)
