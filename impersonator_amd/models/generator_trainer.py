@@ -12,7 +12,12 @@ the Liquid Warping Block) keeps what its gradient needs and runs the op-level HI
 InstanceNorm-affine forward/backward, grid_sample and its input gradient, Adam).  torch only carries tensors between
 them (views, cat/split, a handful of elementwise expressions of the loss on 3- and 1-channel images).
 Parameters, gradients and Adam moments live in flat buffers; the gradient buffer is what a data-parallel job averages
-(`sharding.average_gradients`, RCCL) before `step()`."""
+(`sharding.average_gradients`, RCCL) before `step()`.
+
+What the cycle fine-tune (models/post_tune.py) runs as well is stated here once: `GeneratorParams` (the device layout of
+`param_layout`, the flat buffers, `first_write`), `_TwoStream` (the source / transfer pass with the Liquid Warping Block and
+its backward: which layer's gradient goes where, and in which order), `_l1` / `_bce`, `head_rect`.  `GeneratorTrainer` adds
+BGNet (`_BGNet`), the discriminator and loss networks, the gradient buckets and Adam over the whole buffer."""
 import torch
 
 from .. import ops, sharding
@@ -45,7 +50,7 @@ class _ConvIN(object):
     def backward(self, dy, need_dx=True):
         P, G, tr = self.tr.P, self.tr.G, self.tr
         # a parameter's FIRST gradient contribution of an iteration is written straight into its slice of the flat gradient buffer
-        # (GeneratorTrainer.first_write); a further one (none today: every layer runs once per iteration) would be added
+        # (GeneratorParams.first_write); a further one (none today: every layer runs once per iteration) would be added
         og, ob, ow = tr.first_write(self.gkey), tr.first_write(self.bkey), tr.first_write(self.wkey)
         draw, dg, db = ops.instance_norm_backward(self.raw, self.y if self.relu else None, dy.contiguous(), self.stats, P[self.gkey],
                                                   out_dgamma=og, out_dbeta=ob)
@@ -147,51 +152,167 @@ class _ResUnet(object):
         return d, d_skips
 
 
-class GeneratorTrainer(object):
-    """One Adam optimiser over the ImpersonatorGenerator's 194 parameter tensors with a hand-written backward pass."""
+class _BGNet(object):
+    """BGNet (generator.py:80-133): a plain encoder / trunk / decoder with one colour head; its input is data."""
 
-    def __init__(self, generator, discriminator, lambda_D_prob=1.0, lambda_rec=10.0, lambda_tsf=10.0, lambda_mask=0.1,
-                 lambda_mask_smooth=1e-5, lr=0.0002, betas=(0.5, 0.999), eps=1e-8, conv_precision="fp32", mask_bce=False,
-                 bg_both=False, vgg=None, face=None, lambda_face=1.0, use_vgg=None, use_style=False,
-                 lambda_style=5.0):
-        """conv_precision 'bf16x3': the convolutions of the three streams (forward, data gradient, weight gradient) run on
-        split-bf16 operands (include/lwg.h, lwg_conv2d_desc.precision); norms, heads, losses, Adam: fp32."""
+    def __init__(self, tr, repeat):
+        self.enc = [_ConvIN(tr, "bg_model.model.0.weight", "bg_model.model.1", 1, 3)]
+        self.enc += [_ConvIN(tr, "bg_model.model.%d.weight" % (3 + 3 * i), "bg_model.model.%d" % (4 + 3 * i), 2, 1)
+                     for i in range(N_DOWN)]
+        r0 = 3 + 3 * N_DOWN
+        self.res = [_Res(tr, "bg_model.model.%d" % (r0 + i)) for i in range(repeat)]
+        u0 = r0 + repeat
+        self.dec = [_ConvIN(tr, "bg_model.model.%d.weight" % (u0 + 3 * i), "bg_model.model.%d" % (u0 + 3 * i + 1), 2, 1,
+                            transposed=True) for i in range(N_DOWN)]
+        self.head = _Head(tr, "heads:bg")
+
+    def forward(self, x):
+        for m in self.enc + self.res + self.dec:
+            x = m.forward(x)
+        return self.head.forward(x)[0]
+
+    def backward(self, d_img):
+        d = self.head.backward(d_img)
+        mods = self.enc + self.res + self.dec
+        for m in reversed(mods[1:]):
+            d = m.backward(d)
+        mods[0].backward(d, need_dx=False)
+
+
+class _TwoStream(object):
+    """One ImpersonatorGenerator.infer_front (networks/generator.py:216-243) with its own activations: the source ResUnet and
+    the transfer ResUnet with the Liquid Warping Block, a layer tree over `tr`'s parameters.  `src_decoder=False`: the source
+    stream's decoder and heads are left out (nothing reads the cycle pass's source image, models/imitator.py:400,406)."""
+
+    def __init__(self, tr, src_decoder=True):
+        self.tr, self.src_decoder = tr, src_decoder
+        self.src = _ResUnet(tr, "src_model", tr.repeat)
+        self.tsf = _ResUnet(tr, "tsf_model", tr.repeat)
+
+    def forward(self, src_inputs, tsf_inputs, T):
+        """src_inputs, tsf_inputs (N,H,W,8) NHWC (6 channels + 2 of padding), T (N,H,W,2) -> (src_img, src_mask, tsf_img, tsf_mask)
+        NHWC, the source pair None without its decoder."""
+        tr = self.tr
+        x = src_inputs
+        self.src_enc = []    # features kept for the Liquid Warping Block
+        for m in self.src.enc:
+            x = m.forward(x)
+            self.src_enc.append(x)
+        self.src_res = []
+        for m in self.src.res:
+            x = m.forward(x)
+            self.src_res.append(x)
+        src_img, src_mask = self.src.decode_regress(x, self.src_enc) if self.src_decoder else (None, None)
+        self.Ts = tr._T_levels(T)
+        x = self.tsf.enc[0].forward(tsf_inputs)
+        tsf_enc = [x]
+        for i in range(1, N_DOWN + 1):
+            x = self.tsf.enc[i].forward(x) + ops.grid_sample_nhwc(self.src_enc[i], self.Ts[i], tr.align)
+            tsf_enc.append(x)
+        for i in range(tr.repeat):
+            x = self.tsf.res[i].forward(x) + ops.grid_sample_nhwc(self.src_res[i], self.Ts[N_DOWN], tr.align)
+        tsf_img, tsf_mask = self.tsf.decode_regress(x, tsf_enc)
+        return src_img, src_mask, tsf_img, tsf_mask
+
+    def backward(self, d_src_img, d_src_mask, d_tsf_img, d_tsf_mask, need_dx):
+        """Gradients wrt the four outputs -> parameter gradients into `tr`'s buffer; with `need_dx` returns
+        (d src_inputs, d tsf_inputs), (N,H,W,8) each, through the stems' data gradient."""
+        tr = self.tr
+        d, d_skips = self.tsf.decode_regress_backward(d_tsf_img, d_tsf_mask)
+        # one deterministic scatter plan per pyramid level (the trunk's warps share the 1/8-resolution flow)
+        plans = {l: ops.GridSamplePlan(self.Ts[l], tuple(self.src_enc[l].shape), tr.align) for l in range(1, N_DOWN + 1)}
+        g_res = [None] * tr.repeat
+        for i in reversed(range(tr.repeat)):
+            g_res[i] = ops.grid_sample_backward(d.contiguous(), self.Ts[N_DOWN], tuple(self.src_res[i].shape), tr.align, plan=plans[N_DOWN])
+            d = self.tsf.res[i].backward(d)
+        g_enc = [None] * (N_DOWN + 1)
+        for i in reversed(range(1, N_DOWN + 1)):
+            if i < N_DOWN:
+                d = d + d_skips[i]
+            g_enc[i] = ops.grid_sample_backward(d.contiguous(), self.Ts[i], tuple(self.src_enc[i].shape), tr.align, plan=plans[i])
+            d = self.tsf.enc[i].backward(d)
+        dx_tsf = self.tsf.enc[0].backward(d + d_skips[0], need_dx=need_dx)
+        # source stream: its own decoder and heads (when it has them) plus the Liquid Warping Block gradients
+        if self.src_decoder:
+            d, d_skips = self.src.decode_regress_backward(d_src_img, d_src_mask)
+        else:
+            d, d_skips = None, [None] * N_DOWN
+        for i in reversed(range(tr.repeat)):
+            d = self.src.res[i].backward(g_res[i] if d is None else d + g_res[i])
+        for i in reversed(range(1, N_DOWN + 1)):
+            d = d + g_enc[i]
+            if i < N_DOWN and d_skips[i] is not None:
+                d = d + d_skips[i]
+            d = self.src.enc[i].backward(d)
+        dx_src = self.src.enc[0].backward(d if d_skips[0] is None else d + d_skips[0], need_dx=need_dx)
+        return dx_src, dx_tsf
+
+
+def _l1(a, b, weight):
+    """weight * mean|a - b| and its gradient wrt a"""
+    diff = a - b
+    return diff.abs().mean() * weight, torch.sign(diff) * (weight / diff.numel())
+
+
+def _bce(masks, target, weight):
+    """torch.nn.BCELoss (logs clamped at -100) of `masks` against `target`: the mean, unweighted, and `weight` x its gradient
+    wrt masks"""
+    lm, l1m = torch.log(masks).clamp_(min=-100.0), torch.log1p(-masks).clamp_(min=-100.0)
+    term = -(target * lm + (1 - target) * l1m).mean()
+    return term, ((1 - target) / (1 - masks).clamp_(min=1e-12) - target / masks.clamp(min=1e-12)) * (weight / masks.numel())
+
+
+def head_rect(kps, height, width):
+    """FaceLoss.find_head_rect (networks/networks.py:336-364) and, at height == width, BodyRecoveryFlow.cal_head_bbox
+    (models/impersonator_trainer.py:89-130): kps (N,19,2) in [-1,1] -> (N,4) long (min_x, max_x, min_y, max_y); the head joints
+    are 12.. (NECK_IDS)."""
+    kps = (kps + 1) / 2.0
+    zeros, ones = torch.zeros_like(kps[:, 12, 0]), torch.ones_like(kps[:, 12, 0])
+    min_x = (torch.max(torch.min(kps[:, 12:, 0] - 0.05, dim=1)[0], zeros) * width).long()
+    max_x = (torch.min(torch.max(kps[:, 12:, 0] + 0.05, dim=1)[0], ones) * width).long()
+    min_y = (torch.max(torch.min(kps[:, 12:, 1] - 0.05, dim=1)[0], zeros) * height).long()
+    max_y = (torch.min(torch.max(kps[:, 12:, 1], dim=1)[0], ones) * height).long()
+    return torch.stack([min_x, max_x, min_y, max_y], dim=1)
+
+
+def param_layout(shapes, repeat):
+    """Device layout of every trainable tensor, from the state_dict's shapes {key: shape} (in its order) and the trunk depth:
+    [(device key, device shape, [(state_dict key, row slice, in-channel count)])].  It is the state_dict's layout, except the 7x7
+    stems (input channels padded to 8) and the few-channel 7x7 heads (colour + mask combined, padded to HEAD_ROWS output rows)."""
+    bg_head = "bg_model.model.%d.weight" % (3 + 3 * N_DOWN + repeat + 3 * N_DOWN)
+    spec = []
+    for k, shape in shapes.items():
+        if k.endswith("img_reg.0.weight"):
+            p = k[:-len(".img_reg.0.weight")]
+            spec.append(("heads:" + p, (HEAD_ROWS, 64, 7, 7), [(k, slice(0, 3), 64), (p + ".attetion_reg.0.weight", slice(3, 4), 64)]))
+        elif k.endswith("attetion_reg.0.weight"):
+            continue
+        elif k == bg_head:
+            spec.append(("heads:bg", (HEAD_ROWS, 64, 7, 7), [(k, slice(0, 3), 64)]))
+        elif len(shape) == 4 and shape[2] == 7:
+            spec.append((k, (shape[0], 8, 7, 7), [(k, slice(0, shape[0]), shape[1])]))
+        else:
+            spec.append((k, tuple(shape), [(k, None, None)]))
+    return spec
+
+
+class GeneratorParams(object):
+    """The ImpersonatorGenerator's 194 parameter tensors in their device layout (param_layout): parameters, gradients and Adam
+    moments in four flat buffers with per-tensor views `P` / `G`, and the bookkeeping of a hand-written backward pass over them.
+    What GeneratorTrainer and PostTuner (models/post_tune.py) share."""
+
+    def __init__(self, generator, conv_precision="fp32", device=None):
+        """conv_precision 'bf16x3': the convolutions of the streams (forward, data gradient, weight gradient) run on
+        split-bf16 operands (include/lwg.h, lwg_conv2d_desc.precision); norms, heads, losses, Adam: fp32.
+        `device`: where the buffers live, the current CUDA device by default."""
         if conv_precision not in ops.PRECISIONS:
             raise ValueError("conv_precision must be one of %s" % sorted(ops.PRECISIONS))
-        self.conv_precision = conv_precision
-        # impersonator_trainer.py:251-254 (--mask_bce: BCELoss on the masks), :333-339 (--bg_both: BGNet on the source's
-        # and the target's background, 2N inputs), :256-260 + :376-377 (--use_vgg: `vgg` = networks.vgg.Vgg19Perceptual)
-        # :268-273 + :383-385 (--use_face: `face` = networks.facenet.SphereFaceLoss; the batch then carries 'head_bbox')
-        # `vgg` also serves :262-267 + :379-381 (--use_style: Gram-matrix term, use_style=True); use_vgg=False keeps the L1
-        # transfer term while the network is only there for the style term
-        self.mask_bce, self.bg_both, self.vgg, self.face = bool(mask_bce), bool(bg_both), vgg, face
-        self.use_vgg = (vgg is not None) if use_vgg is None else bool(use_vgg)
-        self.use_style, self.lambda_style, self.lambda_face = bool(use_style), lambda_style, lambda_face
-        if (self.use_vgg or self.use_style) and vgg is None:
-            raise ValueError("use_vgg / use_style need `vgg` (networks.vgg.Vgg19Perceptual)")
-        self.generator, self.D = generator, discriminator
-        self.lam = dict(adv=lambda_D_prob, rec=lambda_rec, tsf=lambda_tsf, mask=lambda_mask, smooth=lambda_mask_smooth)
-        self.lr, self.betas, self.eps, self.t = lr, betas, eps, 0
-        self.t_dev = None   # use_device_step(): Adam's step count on the device (graph replay)
+        self.conv_precision, self.generator = conv_precision, generator
         self.repeat = generator.repeat_num
         self.align = bool(generator.align_corners)
-        dev = torch.device("cuda", torch.cuda.current_device())
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         sd = {k: v.detach().float() for k, v in generator.state_dict().items()}
-        # device layout of every trainable tensor: state_dict layout, except 7x7 stems (input channels padded to 8)
-        # and the few-channel 7x7 heads (colour + mask combined, padded to HEAD_ROWS output rows)
-        self.spec = []   # (device key, shape, [(state_dict key, row slice, in-channel count)])
-        for k, v in sd.items():
-            if k.endswith("img_reg.0.weight"):
-                p = k[:-len(".img_reg.0.weight")]
-                self.spec.append(("heads:" + p, (HEAD_ROWS, 64, 7, 7), [(k, slice(0, 3), 64), (p + ".attetion_reg.0.weight", slice(3, 4), 64)]))
-            elif k.endswith("attetion_reg.0.weight"):
-                continue
-            elif k == "bg_model.model.%d.weight" % (3 + 3 * N_DOWN + self.repeat + 3 * N_DOWN):
-                self.spec.append(("heads:bg", (HEAD_ROWS, 64, 7, 7), [(k, slice(0, 3), 64)]))
-            elif v.dim() == 4 and v.shape[2] == 7:
-                self.spec.append((k, (v.shape[0], 8, 7, 7), [(k, slice(0, v.shape[0]), v.shape[1])]))
-            else:
-                self.spec.append((k, tuple(v.shape), [(k, None, None)]))
+        self.spec = param_layout({k: tuple(v.shape) for k, v in sd.items()}, self.repeat)
         n = sum(int(torch.Size(s).numel()) for _, s, _ in self.spec)
         self.flat_p = torch.zeros(n, device=dev)
         self.flat_g = torch.zeros(n, device=dev)
@@ -199,7 +320,7 @@ class GeneratorTrainer(object):
         self.flat_v = torch.zeros(n, device=dev)
         self._untouched = set()   # gradient slices nothing has been written to in the current backward pass (see first_write)
         self._ranges = []         # (key, lo, hi) element ranges of the flat buffers, in layout order (sharding.GradientBuckets)
-        self._buckets = None
+        self._buckets = None      # only a data-parallel GeneratorTrainer ever has them
         self.P, self.G, off = {}, {}, 0
         for key, shape, parts in self.spec:
             cnt = int(torch.Size(shape).numel())
@@ -213,17 +334,11 @@ class GeneratorTrainer(object):
                     self.P[key].copy_(src)
                 else:
                     self.P[key][rows, :cin].copy_(src)
-        self.bg_enc = [_ConvIN(self, "bg_model.model.0.weight", "bg_model.model.1", 1, 3)]
-        self.bg_enc += [_ConvIN(self, "bg_model.model.%d.weight" % (3 + 3 * i), "bg_model.model.%d" % (4 + 3 * i), 2, 1)
-                        for i in range(N_DOWN)]
-        r0 = 3 + 3 * N_DOWN
-        self.bg_res = [_Res(self, "bg_model.model.%d" % (r0 + i)) for i in range(self.repeat)]
-        u0 = r0 + self.repeat
-        self.bg_dec = [_ConvIN(self, "bg_model.model.%d.weight" % (u0 + 3 * i), "bg_model.model.%d" % (u0 + 3 * i + 1), 2, 1,
-                               transposed=True) for i in range(N_DOWN)]
-        self.bg_head = _Head(self, "heads:bg")
-        self.src = _ResUnet(self, "src_model", self.repeat)
-        self.tsf = _ResUnet(self, "tsf_model", self.repeat)
+
+    def zero_grads(self):
+        """Start of a backward pass: every gradient slice is zero and unwritten."""
+        self.flat_g.zero_()
+        self._untouched = set(self.G)
 
     def first_write(self, key):
         """The gradient slice of `key` if nothing has been written to it in this backward pass yet (then the kernel writes there
@@ -239,6 +354,51 @@ class GeneratorTrainer(object):
         """Called by a layer's backward once the kernels that write its gradients are enqueued (see sharding.GradientBuckets)."""
         if self._buckets is not None:
             self._buckets.checkpoint()
+
+    def _unpacked(self, views):
+        out = {}
+        for key, _, parts in self.spec:
+            for sk, rows, cin in parts:
+                out[sk] = (views[key] if rows is None else views[key][rows, :cin]).detach().cpu().clone()
+        return out
+
+    def state_dict(self):
+        """Current parameters in the generator's state_dict layout (CPU tensors)."""
+        return self._unpacked(self.P)
+
+    def gradients(self):
+        """Gradients of the last backward pass, in the same layout."""
+        return self._unpacked(self.G)
+
+    def _T_levels(self, T):
+        return [None] + [self.generator.resize_trans(torch.empty(1, 1, T.shape[1] >> l, T.shape[2] >> l), T) for l in range(1, N_DOWN + 1)]
+
+
+class GeneratorTrainer(GeneratorParams):
+    """One Adam optimiser over the ImpersonatorGenerator's 194 parameter tensors with a hand-written backward pass."""
+
+    def __init__(self, generator, discriminator, lambda_D_prob=1.0, lambda_rec=10.0, lambda_tsf=10.0, lambda_mask=0.1,
+                 lambda_mask_smooth=1e-5, lr=0.0002, betas=(0.5, 0.999), eps=1e-8, conv_precision="fp32", mask_bce=False,
+                 bg_both=False, vgg=None, face=None, lambda_face=1.0, use_vgg=None, use_style=False,
+                 lambda_style=5.0):
+        super().__init__(generator, conv_precision)
+        # impersonator_trainer.py:251-254 (--mask_bce: BCELoss on the masks), :333-339 (--bg_both: BGNet on the source's
+        # and the target's background, 2N inputs), :256-260 + :376-377 (--use_vgg: `vgg` = networks.vgg.Vgg19Perceptual)
+        # :268-273 + :383-385 (--use_face: `face` = networks.facenet.SphereFaceLoss; the batch then carries 'head_bbox')
+        # `vgg` also serves :262-267 + :379-381 (--use_style: Gram-matrix term, use_style=True); use_vgg=False keeps the L1
+        # transfer term while the network is only there for the style term
+        self.mask_bce, self.bg_both, self.vgg, self.face = bool(mask_bce), bool(bg_both), vgg, face
+        self.use_vgg = (vgg is not None) if use_vgg is None else bool(use_vgg)
+        self.use_style, self.lambda_style, self.lambda_face = bool(use_style), lambda_style, lambda_face
+        if (self.use_vgg or self.use_style) and vgg is None:
+            raise ValueError("use_vgg / use_style need `vgg` (networks.vgg.Vgg19Perceptual)")
+        self.D = discriminator
+        self.lam = dict(adv=lambda_D_prob, rec=lambda_rec, tsf=lambda_tsf, mask=lambda_mask, smooth=lambda_mask_smooth)
+        self.lr, self.betas, self.eps, self.t = lr, betas, eps, 0
+        self.t_dev = None   # use_device_step(): Adam's step count on the device (graph replay)
+        self.bg = _BGNet(self, self.repeat)
+        self.streams = _TwoStream(self)
+        self.src, self.tsf = self.streams.src, self.streams.tsf
 
     def _begin_buckets(self, all_reduce=True):
         """Data-parallel job: the gradient all-reduce runs bucket by bucket on a side stream while the backward pass goes on
@@ -262,58 +422,18 @@ class GeneratorTrainer(object):
         if self._buckets is not None and not self._buckets.joined:
             self._buckets.finish()
 
-    # ------------------------------------------------------------------ parameters
-    def state_dict(self):
-        """Current parameters in the generator's state_dict layout (CPU tensors)."""
-        out = {}
-        for key, _, parts in self.spec:
-            for sk, rows, cin in parts:
-                out[sk] = (self.P[key] if rows is None else self.P[key][rows, :cin]).detach().cpu().clone()
-        return out
-
     def gradients(self):
         self._join_buckets()
-        out = {}
-        for key, _, parts in self.spec:
-            for sk, rows, cin in parts:
-                out[sk] = (self.G[key] if rows is None else self.G[key][rows, :cin]).detach().cpu().clone()
-        return out
+        return super().gradients()
 
     # ------------------------------------------------------------------ forward (impersonator_trainer.py:329-348)
-    def _T_levels(self, T):
-        return [None] + [self.generator.resize_trans(torch.empty(1, 1, T.shape[1] >> l, T.shape[2] >> l), T) for l in range(1, N_DOWN + 1)]
-
     @torch.no_grad()
     def forward(self, batch):
         b = {k: (v.cuda().float() if k != "head_bbox" else v) for k, v in batch.items()}
         self.b = b
-        # --- BGNet
-        x = _nhwc(b["input_G_bg"], 8)
-        for m in self.bg_enc + self.bg_res + self.bg_dec:
-            x = m.forward(x)
-        self.bg_img = self.bg_head.forward(x)[0]
-        # --- source stream (features kept for the Liquid Warping Block)
-        x = _nhwc(b["input_G_src"], 8)
-        self.src_enc = []
-        for m in self.src.enc:
-            x = m.forward(x)
-            self.src_enc.append(x)
-        self.src_res = []
-        for m in self.src.res:
-            x = m.forward(x)
-            self.src_res.append(x)
-        src_img, src_mask = self.src.decode_regress(x, self.src_enc)
-        # --- transfer stream (generator.py:216-243)
-        Ts = self._T_levels(b["T"].contiguous())
-        self.Ts = Ts
-        x = self.tsf.enc[0].forward(_nhwc(b["input_G_tsf"], 8))
-        tsf_enc = [x]
-        for i in range(1, N_DOWN + 1):
-            x = self.tsf.enc[i].forward(x) + ops.grid_sample_nhwc(self.src_enc[i], Ts[i], self.align)
-            tsf_enc.append(x)
-        for i in range(self.repeat):
-            x = self.tsf.res[i].forward(x) + ops.grid_sample_nhwc(self.src_res[i], Ts[N_DOWN], self.align)
-        tsf_img, tsf_mask = self.tsf.decode_regress(x, tsf_enc)
+        self.bg_img = self.bg.forward(_nhwc(b["input_G_bg"], 8))
+        src_img, src_mask, tsf_img, tsf_mask = self.streams.forward(_nhwc(b["input_G_src"], 8), _nhwc(b["input_G_tsf"], 8),
+                                                                    b["T"].contiguous())
         # --- blends (bg_both=False: one background, from the source's inputs)
         n = src_img.shape[0]
         if self.bg_img.shape[0] != (2 * n if self.bg_both else n):
@@ -331,8 +451,7 @@ class GeneratorTrainer(object):
         underneath this pass (sharding.GradientBuckets).  backward(all_reduce=False) leaves this rank's own gradients in flat_g."""
         b, lam = self.b, self.lam
         self._begin_buckets(all_reduce)
-        self.flat_g.zero_()
-        self._untouched = set(self.G)
+        self.zero_grads()
         to_nhwc = lambda t: t.permute(0, 2, 3, 1)
         src_img, src_mask, tsf_img, tsf_mask = self.src.img, self.src.mask, self.tsf.img, self.tsf.mask
         n = src_img.shape[0]
@@ -343,17 +462,14 @@ class GeneratorTrainer(object):
         terms = dict(g_adv=adv * lam["adv"])
         d_ft = to_nhwc(d_in[:, 0:3]) * lam["adv"]
         # L1 terms
-        diff_s = self.fake_src - to_nhwc(b["real_src"])
-        diff_t = self.fake_tsf - to_nhwc(b["real_tsf"])
-        terms["g_rec"] = diff_s.abs().mean() * lam["rec"]
-        d_fs = torch.sign(diff_s) * (lam["rec"] / diff_s.numel())
+        terms["g_rec"], d_fs = _l1(self.fake_src, to_nhwc(b["real_src"]), lam["rec"])
         if self.use_vgg:
             v_loss, v_grad = self.vgg.loss_and_grad(self.fake_tsf.contiguous(), to_nhwc(b["real_tsf"]).contiguous())
             terms["g_tsf"] = v_loss * lam["tsf"]
             d_ft = d_ft + v_grad * lam["tsf"]
         else:
-            terms["g_tsf"] = diff_t.abs().mean() * lam["tsf"]
-            d_ft = d_ft + torch.sign(diff_t) * (lam["tsf"] / diff_t.numel())
+            terms["g_tsf"], d_l1 = _l1(self.fake_tsf, to_nhwc(b["real_tsf"]), lam["tsf"])
+            d_ft = d_ft + d_l1
         if self.use_style:
             s_loss, s_grad = self.vgg.style_loss_and_grad(self.fake_tsf.contiguous(), to_nhwc(b["real_tsf"]).contiguous())
             terms["g_style"] = s_loss * self.lambda_style
@@ -365,10 +481,9 @@ class GeneratorTrainer(object):
         # mask terms on cat([src_mask, tsf_mask])
         masks = torch.cat([src_mask, tsf_mask], dim=0)
         target = to_nhwc(b["bg_mask"])
-        if self.mask_bce:   # torch.nn.BCELoss: logs clamped at -100
-            lm, l1m = torch.log(masks).clamp_(min=-100.0), torch.log1p(-masks).clamp_(min=-100.0)
-            terms["g_mask"] = -(target * lm + (1 - target) * l1m).mean() * lam["mask"]
-            d_masks = ((1 - target) / (1 - masks).clamp_(min=1e-12) - target / masks.clamp(min=1e-12)) * (lam["mask"] / masks.numel())
+        if self.mask_bce:
+            m_term, d_masks = _bce(masks, target, lam["mask"])
+            terms["g_mask"] = m_term * lam["mask"]
         else:
             dm = masks - target
             terms["g_mask"] = (dm * dm).mean() * lam["mask"]
@@ -388,42 +503,9 @@ class GeneratorTrainer(object):
         d_src_img = d_fs * (1 - src_mask)
         d_tsf_img = d_ft * (1 - tsf_mask)
         d_bg = torch.cat([d_fs * src_mask, d_ft * tsf_mask], dim=0) if self.bg_both else d_fs * src_mask + d_ft * tsf_mask
-        # --- transfer stream
-        d, d_skips = self.tsf.decode_regress_backward(d_tsf_img, d_tsf_mask)
-        g_res = [None] * self.repeat
-        # one deterministic scatter plan per pyramid level (the trunk's seven warps share the 1/8-resolution flow)
-        # (env LWG_GS_ATOMIC=1: the float-atomic scatter instead, an A/B switch)
-        import os
-        atomic = os.environ.get("LWG_GS_ATOMIC", "0") == "1"
-        plans = {l: None if atomic else ops.GridSamplePlan(self.Ts[l], tuple(self.src_enc[l].shape), self.align)
-                 for l in range(1, N_DOWN + 1)}
-        for i in reversed(range(self.repeat)):
-            g_res[i] = ops.grid_sample_backward(d.contiguous(), self.Ts[N_DOWN], tuple(self.src_res[i].shape), self.align,
-                                                plan=plans[N_DOWN], deterministic=not atomic)
-            d = self.tsf.res[i].backward(d)
-        g_enc = [None] * (N_DOWN + 1)
-        for i in reversed(range(1, N_DOWN + 1)):
-            if i < N_DOWN:
-                d = d + d_skips[i]
-            g_enc[i] = ops.grid_sample_backward(d.contiguous(), self.Ts[i], tuple(self.src_enc[i].shape), self.align, plan=plans[i],
-                                                deterministic=not atomic)
-            d = self.tsf.enc[i].backward(d)
-        self.tsf.enc[0].backward(d + d_skips[0], need_dx=False)
-        # --- source stream: its own decoder/heads plus the Liquid Warping Block gradients
-        d, d_skips = self.src.decode_regress_backward(d_src_img, d_src_mask)
-        for i in reversed(range(self.repeat)):
-            d = self.src.res[i].backward(d + g_res[i])
-        for i in reversed(range(1, N_DOWN + 1)):
-            d = d + g_enc[i]
-            if i < N_DOWN:
-                d = d + d_skips[i]
-            d = self.src.enc[i].backward(d)
-        self.src.enc[0].backward(d + d_skips[0], need_dx=False)
-        # --- BGNet
-        d = self.bg_head.backward(d_bg)
-        mods = self.bg_enc + self.bg_res + self.bg_dec
-        for j in reversed(range(len(mods))):
-            d = mods[j].backward(d) if j > 0 else mods[j].backward(d, need_dx=False)
+        # --- the transfer and source streams (their inputs are data: no gradient through the stems), then BGNet
+        self.streams.backward(d_src_img, d_src_mask, d_tsf_img, d_tsf_mask, need_dx=False)
+        self.bg.backward(d_bg)
         self.terms = terms
         return terms
 

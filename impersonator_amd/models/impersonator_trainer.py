@@ -13,7 +13,7 @@ from ..networks.discriminator import PatchDiscriminator
 from ..networks.generator import ImpersonatorGenerator
 from ..networks.facenet import SphereFaceLoss
 from ..networks.vgg import Vgg19Perceptual
-from .generator_trainer import GeneratorTrainer
+from .generator_trainer import GeneratorTrainer, head_rect
 from .models import BaseModel
 
 
@@ -67,15 +67,8 @@ class BodyRecoveryFlow(torch.nn.Module):
                 self.cal_head_bbox(ref_info['j2d']), self.cal_body_bbox(ref_info['j2d']))
 
     def cal_head_bbox(self, kps):
-        """:89-130: kps (N,19,2) in [-1,1] -> (N,4) long [min_x, max_x, min_y, max_y]; the head joints are 12.. (NECK_IDS)."""
-        size = self._opt.image_size
-        kps = (kps + 1) / 2.0
-        zeros, ones = torch.zeros_like(kps[:, 12, 0]), torch.ones_like(kps[:, 12, 0])
-        min_x = torch.max(torch.min(kps[:, 12:, 0] - 0.05, dim=1)[0], zeros)
-        max_x = torch.min(torch.max(kps[:, 12:, 0] + 0.05, dim=1)[0], ones)
-        min_y = torch.max(torch.min(kps[:, 12:, 1] - 0.05, dim=1)[0], zeros)
-        max_y = torch.min(torch.max(kps[:, 12:, 1], dim=1)[0], ones)
-        return torch.stack([(v * size).long() for v in (min_x, max_x, min_y, max_y)], dim=1)
+        """:89-130: kps (N,19,2) in [-1,1] -> (N,4) long [min_x, max_x, min_y, max_y]: the head rectangle of a square image."""
+        return head_rect(kps, self._opt.image_size, self._opt.image_size)
 
     def cal_body_bbox(self, kps, factor=1.2):
         """:132-170."""

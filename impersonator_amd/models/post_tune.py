@@ -2,8 +2,9 @@
 (models/imitator.py:344-472) and the samples it trains on (run_imitator.py:21-163, data/dataset.py:249-324).
 
 `PostTuner` restates the loop body -- two generator passes over ONE parameter set, the second fed with the first's
-output image, four loss terms, Adam -- on the building blocks of the generator trainer (models/generator_trainer.py):
-hand-written backward pass over the op-level HIP kernels of liblwg, flat parameter / gradient / moment buffers.
+output image, four loss terms, Adam -- on what models/generator_trainer.py states once for both trainers: the parameter
+store (GeneratorParams: device layout, flat parameter / gradient / moment buffers, `first_write`), the two-stream pass
+with its hand-written backward over the op-level HIP kernels of liblwg (_TwoStream) and the L1 / BCE loss pieces.
 What is new underneath is the data gradient of the 7x7 stems (include/lwg.h, lwg_conv2d_backward_data's few-channel
 case): the cycle pass's stems read an image the first pass produced, so the gradient has to go through them.
 
@@ -12,84 +13,10 @@ import torch
 
 from .. import ops
 from ..utils import util
-from .generator_trainer import GeneratorTrainer, N_DOWN, _ResUnet, _nhwc
+from .generator_trainer import GeneratorParams, _TwoStream, _bce, _l1, _nhwc, head_rect
 
 
-class _Pass(object):
-    """One ImpersonatorGenerator.infer_front (networks/generator.py:216-243) with its own activations: a layer tree over the
-    tuner's parameters.  `src_decoder=False`: the source stream's decoder and heads are left out (nothing reads the cycle
-    pass's source image, models/imitator.py:400,406)."""
-
-    def __init__(self, tr, src_decoder=True):
-        self.tr, self.src_decoder = tr, src_decoder
-        self.src = _ResUnet(tr, "src_model", tr.repeat)
-        self.tsf = _ResUnet(tr, "tsf_model", tr.repeat)
-
-    def forward(self, src_inputs, tsf_inputs, T):
-        """src_inputs, tsf_inputs (N,H,W,8) NHWC (6 channels + 2 of padding), T (N,H,W,2) -> (src_img, src_mask, tsf_img, tsf_mask)
-        NHWC, the source pair None without its decoder."""
-        tr = self.tr
-        x = src_inputs
-        self.src_enc = []
-        for m in self.src.enc:
-            x = m.forward(x)
-            self.src_enc.append(x)
-        self.src_res = []
-        for m in self.src.res:
-            x = m.forward(x)
-            self.src_res.append(x)
-        src_img, src_mask = self.src.decode_regress(x, self.src_enc) if self.src_decoder else (None, None)
-        self.Ts = tr._T_levels(T)
-        x = self.tsf.enc[0].forward(tsf_inputs)
-        tsf_enc = [x]
-        for i in range(1, N_DOWN + 1):
-            x = self.tsf.enc[i].forward(x) + ops.grid_sample_nhwc(self.src_enc[i], self.Ts[i], tr.align)
-            tsf_enc.append(x)
-        for i in range(tr.repeat):
-            x = self.tsf.res[i].forward(x) + ops.grid_sample_nhwc(self.src_res[i], self.Ts[N_DOWN], tr.align)
-        tsf_img, tsf_mask = self.tsf.decode_regress(x, tsf_enc)
-        return src_img, src_mask, tsf_img, tsf_mask
-
-    def backward(self, d_src_img, d_src_mask, d_tsf_img, d_tsf_mask, need_dx):
-        """Gradients wrt the four outputs -> parameter gradients into the tuner's buffer; with `need_dx` returns
-        (d src_inputs, d tsf_inputs), (N,H,W,8) each, through the stems' data gradient."""
-        tr = self.tr
-        d, d_skips = self.tsf.decode_regress_backward(d_tsf_img, d_tsf_mask)
-        plans = {l: ops.GridSamplePlan(self.Ts[l], tuple(self.src_enc[l].shape), tr.align) for l in range(1, N_DOWN + 1)}
-        g_res = [None] * tr.repeat
-        for i in reversed(range(tr.repeat)):
-            g_res[i] = ops.grid_sample_backward(d.contiguous(), self.Ts[N_DOWN], tuple(self.src_res[i].shape), tr.align, plan=plans[N_DOWN])
-            d = self.tsf.res[i].backward(d)
-        g_enc = [None] * (N_DOWN + 1)
-        for i in reversed(range(1, N_DOWN + 1)):
-            if i < N_DOWN:
-                d = d + d_skips[i]
-            g_enc[i] = ops.grid_sample_backward(d.contiguous(), self.Ts[i], tuple(self.src_enc[i].shape), tr.align, plan=plans[i])
-            d = self.tsf.enc[i].backward(d)
-        dx_tsf = self.tsf.enc[0].backward(d + d_skips[0], need_dx=need_dx)
-        # source stream: its own decoder and heads (when it has them) plus the Liquid Warping Block gradients
-        if self.src_decoder:
-            d, d_skips = self.src.decode_regress_backward(d_src_img, d_src_mask)
-        else:
-            d, d_skips = None, [None] * N_DOWN
-        for i in reversed(range(tr.repeat)):
-            d = self.src.res[i].backward(g_res[i] if d is None else d + g_res[i])
-        for i in reversed(range(1, N_DOWN + 1)):
-            d = d + g_enc[i]
-            if i < N_DOWN and d_skips[i] is not None:
-                d = d + d_skips[i]
-            d = self.src.enc[i].backward(d)
-        dx_src = self.src.enc[0].backward(d if d_skips[0] is None else d + d_skips[0], need_dx=need_dx)
-        return dx_src, dx_tsf
-
-
-def _l1(a, b, weight):
-    """weight * mean|a - b| and its gradient wrt a"""
-    diff = a - b
-    return diff.abs().mean() * weight, torch.sign(diff) * (weight / diff.numel())
-
-
-class PostTuner(GeneratorTrainer):
+class PostTuner(GeneratorParams):
     """models/imitator.py:344-472 on the device.
 
         tuner = PostTuner(generator, bg, render)
@@ -106,19 +33,19 @@ class PostTuner(GeneratorTrainer):
     FaceLoss.compute_loss detaches its second argument (networks/networks.py:273-286) and post_personalize passes the
     generated image second (:445-446).  It is computed forward-only, when `face` is given, and is not part of `total`'s gradient.
 
-    A GeneratorTrainer for what it shares with it -- the device layout of the parameters, the flat buffers, `first_write`,
-    `state_dict` -- with its own forward / backward / step: no BGNet pass, no discriminator, no all-reduce.
+    No BGNet pass, no discriminator, no all-reduce: personalisation runs on one device.
     """
 
     LR, BETAS, EPS, EPOCHS = 0.0002, (0.5, 0.999), 1e-8, 5       # :415-417; torch.optim.Adam's default eps
     W_CYCLE, W_STRUCT, W_MASK = 10.0, 10.0, 5.0                  # :452
 
     def __init__(self, generator, bg, render, front_warp=False, conv_precision="fp32", face=None):
-        super().__init__(generator, None, lr=self.LR, betas=self.BETAS, eps=self.EPS, conv_precision=conv_precision)
+        super().__init__(generator, conv_precision)
+        self.lr, self.betas, self.eps, self.t = self.LR, self.BETAS, self.EPS, 0
         self.render, self.front_warp, self.face = render, bool(front_warp), face
         dev = self.flat_p.device
         self.bg = _nhwc(torch.as_tensor(bg, dtype=torch.float32).to(dev).reshape((-1, 3) + tuple(bg.shape[-2:])))
-        self.first, self.cycle = _Pass(self, True), _Pass(self, False)
+        self.first, self.cycle = _TwoStream(self, True), _TwoStream(self, False)
         # the slice of the flat buffers Adam steps on: everything but bg_model.* (a contiguous tail of the state_dict's order)
         tuned = [(k, lo, hi) for k, lo, hi in self._ranges if not (k.startswith("bg_model.") or k == "heads:bg")]
         self._lo = tuned[0][1]
@@ -168,9 +95,7 @@ class PostTuner(GeneratorTrainer):
     def backward(self):
         """-> the loss terms (device scalars): cycle, struct, mask (unweighted, as the reference logs them), fid when there is a
         face network, and total = 10 cycle + 10 struct + 5 mask (+ fid, a constant as far as the gradient goes)."""
-        self._buckets = None
-        self.flat_g.zero_()
-        self._untouched = set(self.G)
+        self.zero_grads()
         bg, bh = self.bg, self.back_head
         # cycle reconstruction (:434)
         c1, d_fake_src = _l1(self.fake_src, self.src_real, self.W_CYCLE)
@@ -180,11 +105,9 @@ class PostTuner(GeneratorTrainer):
         s1, d_fake_tsf = _l1(self.fake_tsf, self.preds, self.W_STRUCT)
         s2, d_warp = _l1(self.cyc_warp * bh, self.src_real * body * bh, 2 * self.W_STRUCT)
         d_warp = d_warp * bh
-        # masks (:450), torch.nn.BCELoss: logs clamped at -100
+        # masks (:450)
         masks = torch.cat([self.s_mask, self.t_mask], dim=0)
-        lm, l1m = torch.log(masks).clamp_(min=-100.0), torch.log1p(-masks).clamp_(min=-100.0)
-        m_term = -(self.pseudo * lm + (1 - self.pseudo) * l1m).mean()
-        d_masks = ((1 - self.pseudo) / (1 - masks).clamp_(min=1e-12) - self.pseudo / masks.clamp(min=1e-12)) * (self.W_MASK / masks.numel())
+        m_term, d_masks = _bce(masks, self.pseudo, self.W_MASK)
         n = self.s_mask.shape[0]
         d_s_mask, d_t_mask = d_masks[:n], d_masks[n:]
         terms = dict(cycle=(c1 + c2) / self.W_CYCLE, struct=(s1 + s2) / self.W_STRUCT, mask=m_term)
@@ -237,24 +160,9 @@ class PostTuner(GeneratorTrainer):
         self.step()
         return {k: float(v) for k, v in terms.items()}
 
-    def optimize_G(self, batch):
-        raise TypeError("PostTuner trains on post_personalize's samples: optimize(sample)")
-
     def gradients(self):
         """Gradients of the last backward pass in the state_dict's layout: the two streams' tensors (bg_model.* has none)."""
         return {k: v for k, v in super().gradients().items() if not k.startswith("bg_model.")}
-
-
-def head_rect(kps, height, width):
-    """FaceLoss.find_head_rect (networks/networks.py:336-364): kps (N,19,2) in [-1,1] -> (N,4) long (min_x, max_x, min_y, max_y);
-    the head joints are 12.. (NECK_IDS)."""
-    kps = (kps + 1) / 2.0
-    zeros, ones = torch.zeros_like(kps[:, 12, 0]), torch.ones_like(kps[:, 12, 0])
-    min_x = (torch.max(torch.min(kps[:, 12:, 0] - 0.05, dim=1)[0], zeros) * width).long()
-    max_x = (torch.min(torch.max(kps[:, 12:, 0] + 0.05, dim=1)[0], ones) * width).long()
-    min_y = (torch.max(torch.min(kps[:, 12:, 1] - 0.05, dim=1)[0], zeros) * height).long()
-    max_y = (torch.min(torch.max(kps[:, 12:, 1], dim=1)[0], ones) * height).long()
-    return torch.stack([min_x, max_x, min_y, max_y], dim=1)
 
 
 @torch.no_grad()

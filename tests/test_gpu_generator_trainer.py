@@ -77,7 +77,7 @@ def test_bf16x3_convolutions(setup):
 
 def _relu_layers(tr):
     """every conv -> InstanceNorm -> ReLU block of the three streams, in a fixed order, with its stored activation"""
-    mods = list(tr.bg_enc) + [m for r in tr.bg_res for m in (r.a,)] + list(tr.bg_dec)
+    mods = list(tr.bg.enc) + [m for r in tr.bg.res for m in (r.a,)] + list(tr.bg.dec)
     for st in (tr.src, tr.tsf):
         mods += list(st.enc) + [r.a for r in st.res] + list(st.dec) + list(st.skip)
     return [m for m in mods if m.relu]

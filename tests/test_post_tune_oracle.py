@@ -46,7 +46,7 @@ def test_fid_term_carries_no_gradient():
 
 @needs_reference
 def test_head_rect_equals_the_reference():
-    from impersonator_amd.models.post_tune import head_rect
+    from impersonator_amd.models.generator_trainer import head_rect
     live = reference_loader.load().networks.FaceLoss.find_head_rect
     g = torch.Generator().manual_seed(1)
     for scale in (0.3, 0.8, 1.3):          # 1.3: joints outside the image, the clamps act
