@@ -134,6 +134,7 @@ _PROTOS = {
     "lwg_discriminator_forward": (_i, [_vp, _vp, _i, _vp, _vp]),
     "lwg_discriminator_backward": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
     "lwg_discriminator_buffers": (_i, [_vp, _c.POINTER(_vp), _c.POINTER(_vp), _c.POINTER(_c.c_size_t)]),
+    "lwg_adam_update_scheduled": (_i, [_vp, _vp, _vp, _vp, _c.c_size_t, _vp, _vp, _c.c_int, _c.c_float, _c.c_float, _c.c_float, _vp]),
     "lwg_discriminator_adam_step": (_i, [_vp, _c.c_float, _c.c_float, _c.c_float, _c.c_float, _vp]),
     "lwg_generator_peek": (_i, [_vp, _i, _vp, _sz, _vp]),
     "lwg_generator_profile": (_i, [_vp, _i]),

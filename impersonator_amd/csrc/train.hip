@@ -1238,7 +1238,8 @@ __global__ __launch_bounds__(256) void dgrad_weights_kernel(const float *__restr
 // (advanced by step_inc_kernel in front of this launch) and the bias corrections come from it -- the form a captured graph
 // can replay: a host-side count would be frozen into the launch arguments.  The state carries beta1^t and beta2^t as running
 // products in double (a powf in the kernel would do, but its expansion contains packed-fp32 instructions of the form
-// tests/test_pk_opsel_lint.py bans from this library).
+// tests/test_pk_opsel_lint.py bans from this library).  lr_table != null (with step_dev): the learning rate is device data as
+// well, lr_table[min(t, lr_count) - 1] for the advanced count t -- a schedule that a captured graph replays without re-capture.
 struct AdamStep { long step; double p1, p2; };
 __global__ void step_inc_kernel(AdamStep *s, float b1, float b2)
 {
@@ -1248,13 +1249,18 @@ __global__ void step_inc_kernel(AdamStep *s, float b1, float b2)
 }
 __global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
                                                    float *__restrict__ v, long n, float lr, float b1, float b2, float eps,
-                                                   float bc1, float bc2_sqrt, const AdamStep *__restrict__ step_dev)
+                                                   float bc1, float bc2_sqrt, const AdamStep *__restrict__ step_dev,
+                                                   const float *__restrict__ lr_table, int lr_count)
 {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     if (step_dev) {
         bc1 = 1.f - (float)step_dev->p1;
         bc2_sqrt = sqrtf(1.f - (float)step_dev->p2);
+        if (lr_table) {
+            const long t = step_dev->step;
+            lr = lr_table[t < 1 ? 0 : (t < lr_count ? t : lr_count) - 1];
+        }
     }
     const float gi = g[i];
     const float mi = b1 * m[i] + (1.f - b1) * gi;
@@ -1737,6 +1743,15 @@ __global__ __launch_bounds__(256) void weight_layout_kernel(const float *__restr
     }
 }
 
+// zeroes the padding of a matrix with `rows` rows of `dense` entries at a pitch of `pitch` floats: dst[r][dense .. pitch) <- 0
+__global__ __launch_bounds__(256) void weight_pad_zero_kernel(float *__restrict__ dst, int rows, int dense, int pitch)
+{
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int pad = pitch - dense;
+    if (i >= (long)rows * pad) return;
+    dst[(i / pad) * pitch + dense + i % pad] = 0.f;
+}
+
 // sums the `KS` reduction-split slices of a general-mode conv (ConvArgs::ksplit) in order and adds the bias: y[i] = bias[i % C] + sum_k part[k][i]
 __global__ __launch_bounds__(256) void ksplit_reduce_kernel(const float4 *__restrict__ part, int KS, size_t stride4, long n4, int C,
                                                             const float *__restrict__ bias, float4 *__restrict__ y)
@@ -2211,7 +2226,8 @@ int lwg_discriminator_adam_step(lwg_discriminator *d, float lr, float beta1, flo
         LWG_LAUNCH_CHECK("step_inc_kernel");
     }
     adam_kernel<<<ceil_div((long)d->nparams, 256), 256, 0, st>>>(d->params, d->grads, d->m, d->v, (long)d->nparams, lr, beta1,
-                                                                 beta2, eps, bc1, sqrtf(bc2), d->device_step ? d->step_dev : nullptr);
+                                                                 beta2, eps, bc1, sqrtf(bc2), d->device_step ? d->step_dev : nullptr,
+                                                                 nullptr, 0);
     LWG_LAUNCH_CHECK("adam_kernel");
     return d_refresh_dgrad_weights(d, st);
 }
@@ -2385,7 +2401,12 @@ int relayout(const float *w, float *dst, int mode, int A, int B, int taps, long 
 {
     const int rows = mode == 1 ? B : A, dense = taps * (mode == 1 ? A : B);
     if (split && pitch && pitch != dense) LWG_FAIL(LWG_ERR_STATE, "relayout: split matrices have no row padding");
-    if (pitch && pitch != dense) LWG_HIP(hipMemsetAsync(dst, 0, (size_t)rows * pitch * sizeof(float), st));
+    // the row padding is zeroed by a kernel of this library, not by hipMemsetAsync: the re-layout runs inside captured iterations,
+    // and a replayed graph's memset node left the padding as it found it (NaN bits there turn every output of the conv into NaN)
+    if (pitch && pitch != dense) {
+        weight_pad_zero_kernel<<<ceil_div((long)rows * (pitch - dense), 256), 256, 0, st>>>(dst, rows, dense, pitch);
+        LWG_LAUNCH_CHECK("weight_pad_zero_kernel");
+    }
     // (an LDS-tiled transpose -- 32 x 32 x taps tiles, contiguous reads, 128-byte writes -- measured SLOWER in the training iteration:
     // 25.3 vs 24.3 ms at 256x256 batch 4, profiles/r05_train_ab.md: 256 workgroups of 36 serial passes against 9216 independent ones)
     weight_layout_kernel<<<ceil_div(total, 256), 256, 0, st>>>(w, dst, mode, A, B, taps, total, pitch ? pitch : dense, split ? 1 : 0);
@@ -3039,7 +3060,8 @@ int lwg_adam_update(float *param, const float *grad, float *exp_avg, float *exp_
     LWG_REQUIRE(param && grad && exp_avg && exp_avg_sq && step >= 1, "adam_update: bad argument");
     const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
     adam_kernel<<<ceil_div((long)n, 256), 256, 0, reinterpret_cast<hipStream_t>(stream)>>>(param, grad, exp_avg, exp_avg_sq, (long)n,
-                                                                                          lr, beta1, beta2, eps, bc1, sqrtf(bc2), nullptr);
+                                                                                          lr, beta1, beta2, eps, bc1, sqrtf(bc2), nullptr,
+                                                                                          nullptr, 0);
     LWG_LAUNCH_CHECK("adam_kernel");
     return LWG_OK;
 }
@@ -3053,7 +3075,22 @@ int lwg_adam_update_device_step(float *param, const float *grad, float *exp_avg,
     AdamStep *sd = static_cast<AdamStep *>(step_state);
     step_inc_kernel<<<1, 1, 0, st>>>(sd, beta1, beta2);
     LWG_LAUNCH_CHECK("step_inc_kernel");
-    adam_kernel<<<ceil_div((long)n, 256), 256, 0, st>>>(param, grad, exp_avg, exp_avg_sq, (long)n, lr, beta1, beta2, eps, 1.f, 1.f, sd);
+    adam_kernel<<<ceil_div((long)n, 256), 256, 0, st>>>(param, grad, exp_avg, exp_avg_sq, (long)n, lr, beta1, beta2, eps, 1.f, 1.f, sd,
+                                                        nullptr, 0);
+    LWG_LAUNCH_CHECK("adam_kernel");
+    return LWG_OK;
+}
+
+int lwg_adam_update_scheduled(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, size_t n, void *step_state,
+                              const float *lr_table, int lr_count, float beta1, float beta2, float eps, lwg_stream_t stream)
+{
+    LWG_REQUIRE(param && grad && exp_avg && exp_avg_sq && step_state && lr_table && lr_count >= 1, "adam_update_scheduled: bad argument");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    AdamStep *sd = static_cast<AdamStep *>(step_state);
+    step_inc_kernel<<<1, 1, 0, st>>>(sd, beta1, beta2);
+    LWG_LAUNCH_CHECK("step_inc_kernel");
+    adam_kernel<<<ceil_div((long)n, 256), 256, 0, st>>>(param, grad, exp_avg, exp_avg_sq, (long)n, 0.f, beta1, beta2, eps, 1.f, 1.f, sd,
+                                                        lr_table, lr_count);
     LWG_LAUNCH_CHECK("adam_kernel");
     return LWG_OK;
 }

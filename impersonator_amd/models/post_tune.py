@@ -8,7 +8,12 @@ with its hand-written backward over the op-level HIP kernels of liblwg (_TwoStre
 What is new underneath is the data gradient of the 7x7 stems (include/lwg.h, lwg_conv2d_backward_data's few-channel
 case): the cycle pass's stems read an image the first pass produced, so the gradient has to go through them.
 
-`meta_samples` builds the training samples on the device, from an Imitator whose source is personalised."""
+`meta_samples` builds the training samples on the device, from an Imitator whose source is personalised.
+
+`SwapTuner` is the Swapper's fine-tune (models/swapper.py:273-476) on the same two passes and the same backward: a background per
+sample, no back-of-head mask, its own face pairs, and 50 iterations on ONE batch of two with a decaying learning rate.  Step
+count, rate table and loss history live on the device (ops.adam_update_scheduled), so the iteration is captured once as a HIP
+graph and replayed.  `swap_samples` builds that batch from a Swapper after swap_setup."""
 import torch
 
 from .. import ops
@@ -53,29 +58,40 @@ class PostTuner(GeneratorParams):
             raise RuntimeError("PostTuner: bg_model's parameters are expected in front of the two streams'")
 
     # ------------------------------------------------------------------ forward (:350-406)
+    # what `load` leaves on the tuner: one batch in device layout, everything the two passes and the loss read besides the parameters
+    DATA = ("src_in", "tsf_in", "T", "T_cycle", "src_real", "preds", "pseudo", "j2d", "back_head", "fm_t", "fm_s")
+
     @torch.no_grad()
-    def forward(self, sample):
-        """`sample`: the reference's keys (data/dataset.py:306-322 + preds, run_imitator.py:151), CPU or CUDA tensors.
-        -> (fake_src, fake_tsf, cycle_tsf, fake_src_mask, fake_tsf_mask) NCHW."""
+    def load(self, sample):
+        """`sample`: the reference's keys (data/dataset.py:306-322 + preds, run_imitator.py:151), CPU or CUDA tensors -> the
+        `DATA` attributes: NHWC float32 on the device, the masks looked up through the renderer."""
         dev = self.flat_p.device
         s = {k: torch.as_tensor(v).to(dev) for k, v in sample.items() if k in (
             "images", "pseudo_masks", "j2d", "T", "T_cycle", "src_inputs", "tsf_inputs", "src_fim", "tsf_fim", "preds")}
         f32 = lambda t: t.float().contiguous()
-        self.s = s
         self.src_in, self.tsf_in = _nhwc(f32(s["src_inputs"]), 8), _nhwc(f32(s["tsf_inputs"]), 8)
         self.T, self.T_cycle = f32(s["T"]), f32(s["T_cycle"])
         self.src_real = _nhwc(f32(s["images"][:, 0]))                                  # :429 (images[:, 1] is not read by the loss)
         self.preds = _nhwc(f32(s["preds"]))
         self.pseudo = _nhwc(f32(torch.cat([s["pseudo_masks"][:, 0], s["pseudo_masks"][:, 1]], dim=0)))   # :362-363
+        self.j2d = f32(s["j2d"])
         mask_of = lambda fim, front: _nhwc(self.render.encode_front_fim(fim, transpose=True, front_fn=front).float())
-        self.back_head = 1 - mask_of(s["tsf_fim"], False)                              # :441
+        self.back_head = self._back_head(mask_of, s)
+        self.fm_t, self.fm_s = (mask_of(s["tsf_fim"], True), mask_of(s["src_fim"], True)) if self.front_warp else (None, None)
+
+    def _back_head(self, mask_of, s):
+        """the mask of the structure term's second half (:441), or None for no mask"""
+        return 1 - mask_of(s["tsf_fim"], False)
+
+    @torch.no_grad()
+    def passes(self):
+        """The two generator passes over the loaded batch -> (fake_src, fake_tsf, cycle_tsf, fake_src_mask, fake_tsf_mask) NCHW."""
         bg = self.bg
         # first pass (:385-392)
         self.s_img, self.s_mask, self.t_img, self.t_mask = self.first.forward(self.src_in, self.tsf_in, self.T)
         self.fake_src = self.s_mask * bg + (1 - self.s_mask) * self.s_img
         self.fake_tsf = self.t_mask * bg + (1 - self.t_mask) * self.t_img
-        if self.front_warp:
-            self.fm_t, self.fm_s = mask_of(s["tsf_fim"], True), mask_of(s["src_fim"], True)
+        if self.front_warp:   # :378-382
             self.fake_tsf = (1 - self.fm_t) * self.fake_tsf + self.tsf_in[..., 0:3] * self.fm_t * (1 - self.t_mask)
         # cycle inputs (:368-376); images travel as 4-channel NHWC through the warp (its kernels take C % 4 == 0)
         self.cyc_warp = ops.grid_sample_nhwc(torch.nn.functional.pad(self.fake_tsf, (0, 1)).contiguous(), self.T_cycle, self.align)[..., 0:3]
@@ -90,6 +106,11 @@ class PostTuner(GeneratorParams):
         nchw = lambda t: t.permute(0, 3, 1, 2).contiguous()
         return nchw(self.fake_src), nchw(self.fake_tsf), nchw(self.cyc_tsf), nchw(self.s_mask), nchw(self.t_mask)
 
+    def forward(self, sample):
+        """`load(sample)` + `passes()` -> (fake_src, fake_tsf, cycle_tsf, fake_src_mask, fake_tsf_mask) NCHW."""
+        self.load(sample)
+        return self.passes()
+
     # ------------------------------------------------------------------ loss (:433-452) and its gradient
     @torch.no_grad()
     def backward(self):
@@ -103,8 +124,11 @@ class PostTuner(GeneratorParams):
         # structure (:437-443): the prior's image, and the warped-back body without the back of the head
         body = 1 - self.src_in[..., 5:6]
         s1, d_fake_tsf = _l1(self.fake_tsf, self.preds, self.W_STRUCT)
-        s2, d_warp = _l1(self.cyc_warp * bh, self.src_real * body * bh, 2 * self.W_STRUCT)
-        d_warp = d_warp * bh
+        if bh is None:
+            s2, d_warp = _l1(self.cyc_warp, self.src_real * body, 2 * self.W_STRUCT)
+        else:
+            s2, d_warp = _l1(self.cyc_warp * bh, self.src_real * body * bh, 2 * self.W_STRUCT)
+            d_warp = d_warp * bh
         # masks (:450)
         masks = torch.cat([self.s_mask, self.t_mask], dim=0)
         m_term, d_masks = _bce(masks, self.pseudo, self.W_MASK)
@@ -139,10 +163,13 @@ class PostTuner(GeneratorParams):
         """:445-446, forward only: the head rectangles are FaceLoss.find_head_rect's (networks/networks.py:336-364) of j2d[:, 0]
         (source) and j2d[:, 1] (prior)."""
         h, w = self.fake_src.shape[1:3]
-        j2d = self.s["j2d"].float()
-        a = self.face.loss_and_grad(self.cyc_tsf.contiguous(), self.src_real, head_rect(j2d[:, 0], h, w))[0]
-        b = self.face.loss_and_grad(self.fake_tsf.contiguous(), self.preds, head_rect(j2d[:, 1], h, w))[0]
+        a = self.face.loss_and_grad(self.cyc_tsf.contiguous(), self.src_real, head_rect(self.j2d[:, 0], h, w))[0]
+        b = self.face.loss_and_grad(self.fake_tsf.contiguous(), self._fid_prior(), head_rect(self.j2d[:, 1], h, w))[0]
         return a + b
+
+    def _fid_prior(self):
+        """what the transfer image is compared with in the face term (:446): the prior's image"""
+        return self.preds
 
     # ------------------------------------------------------------------ Adam (:417, :453-455)
     @torch.no_grad()
@@ -163,6 +190,224 @@ class PostTuner(GeneratorParams):
     def gradients(self):
         """Gradients of the last backward pass in the state_dict's layout: the two streams' tensors (bg_model.* has none)."""
         return {k: v for k, v in super().gradients().items() if not k.startswith("bg_model.")}
+
+
+class SwapTuner(PostTuner):
+    """models/swapper.py:273-476 on the device: PostTuner's two passes, loss and backward, with the Swapper's differences.
+
+        tuner = SwapTuner(generator, bg, render, batch_size=opt.batch_size)
+        tuner.load(swap_samples(swapper))
+        history = tuner.run()
+        generator.load_state_dict(tuner.state_dict())
+
+    `bg` (2,3,H,W) = [src_info['bg'], tsf_info['bg']] (:277): a background per sample.  The structure term has no back-of-head
+    mask (:436-442).  `fid` (:444-445), a readout as in PostTuner, compares (src_imgs, cycle_tsf; j2d[:, 0]) and
+    (tsf_inputs[:, 0:3], fake_tsf; j2d[:, 1]): the WARPED source, not the prior's image.  At bs == 1 the reference crops with row
+    0's key points whichever sample runs (`j2ds[:, 0]` of the whole batch, :444); here the running sample's own row is used.
+    Batch rule (:275, :409-428): bs = 2 if batch_size > 1 else 1; at bs == 1 step s trains on sample s % 2 with
+    pseudo_masks[i:4:2].
+
+    The learning rate (:391-395, :473-474) is `lr_schedule`, a table on the device next to Adam's step count; the four terms of
+    every step go to row `step count` of `history` (total, 4) before the Adam step.  Nothing about a step is host state that a
+    kernel reads, so `optimize_graphed` captures ONE iteration and replays it through all rate changes; `optimize` is the same
+    iteration launched eagerly, without a float read-back.  `terms_history()` is the one read-back, after the loop."""
+
+    TOTAL, FIX, LR_FINAL = 50, 25, 0.00001                       # :391-395
+    TERMS = ("cycle", "struct", "mask", "total")                # columns of `history`
+    # run(): the eager loop.  Replays measured 0-2 % SLOWER at 256x256 (profiles/swap_tune.md: 20-60 ms of kernels per iteration,
+    # not launch-bound)
+    GRAPH = False
+
+    def __init__(self, generator, bg, render, front_warp=False, conv_precision="fp32", face=None, batch_size=2, total=TOTAL, fix=FIX):
+        super().__init__(generator, bg, render, front_warp=front_warp, conv_precision=conv_precision, face=face)
+        if self.bg.shape[0] != 2:
+            raise ValueError("SwapTuner: bg is (2,3,H,W), the two subjects' backgrounds")
+        dev = self.flat_p.device
+        self.bs, self.total, self.bg_pair = (2 if int(batch_size) > 1 else 1), int(total), self.bg   # :275
+        self.lr_table = torch.tensor(self.lr_schedule(total, fix, self.LR, self.LR_FINAL), dtype=torch.float32, device=dev)
+        self.step_state = ops.adam_step_state(0, self.betas, dev)
+        self.history = torch.zeros((self.total, len(self.TERMS)), device=dev)
+        self.fids, self.rows = [], None
+        self._graph = self._graph_terms = self._static = None
+        self._graph_failed, self._graph_warm, self.captures, self.replays = False, 0, 0, 0
+
+    @staticmethod
+    def lr_schedule(total=TOTAL, fix=FIX, init=0.0002, final=0.00001):
+        """The rate each step USES, by the reference's own repeated subtraction: the rate drops by (init - final) / fix after
+        every step > fix (:473-474, :382-389).  50 steps: 2e-4 for steps 0..26, 1.924e-4 at 27, ... 2.52e-5 at 49."""
+        cur, rates = init, []
+        for step in range(int(total)):
+            rates.append(cur)
+            if step > fix:
+                cur -= (init - final) / fix
+        return rates
+
+    def _back_head(self, mask_of, s):
+        return None                                              # :441-442: the whole warped-back body
+
+    def _fid_prior(self):
+        return self.tsf_in[..., 0:3].contiguous()                # :445
+
+    # ------------------------------------------------------------------ the batch (:402-428)
+    @torch.no_grad()
+    def load(self, sample):
+        """The batch of two (`swap_samples`) in device layout, and the rows the steps train on: the batch itself at bs == 2, its
+        two samples in turn at bs == 1 (:409-421)."""
+        self.bg = self.bg_pair
+        super().load(sample)
+        if self.src_in.shape[0] != 2:
+            raise ValueError("SwapTuner trains on the batch of two subjects, got %d samples" % self.src_in.shape[0])
+        whole = {k: getattr(self, k) for k in self.DATA + ("bg",) if getattr(self, k) is not None}
+        if self.bs == 2:
+            self.rows = [whole]
+        else:   # pseudo is cat([source masks, transfer masks]): sample i's pair is rows i and 2 + i (:421)
+            self.rows = [{k: (v[i:4:2] if k == "pseudo" else v[i:i + 1]).contiguous() for k, v in whole.items()} for i in (0, 1)]
+        self._use(self.rows[0])
+
+    def _use(self, row):
+        for k, v in row.items():
+            setattr(self, k, v)
+
+    def _next_row(self):
+        if self.rows is None:
+            raise RuntimeError("SwapTuner: load(sample) first")
+        if self.t >= self.total:
+            raise RuntimeError("SwapTuner: the learning-rate table has %d entries and %d steps are taken" % (self.total, self.t))
+        return self.rows[self.t % len(self.rows)]
+
+    # ------------------------------------------------------------------ one iteration (:429-455)
+    @torch.no_grad()
+    def step(self):
+        """Adam with step count and rate on the device; bg_model.* is not touched"""
+        lo = self._lo
+        ops.adam_update_scheduled(self.flat_p[lo:], self.flat_g[lo:], self.flat_m[lo:], self.flat_v[lo:], self.step_state, self.lr_table,
+                                  self.betas, self.eps)
+
+    @torch.no_grad()
+    def _iteration(self):
+        self.passes()
+        terms = self.backward()
+        # row = the count BEFORE this step's advance, read on the device
+        self.history.index_copy_(0, self.step_state[0:1], torch.stack([terms[k] for k in self.TERMS]).reshape(1, -1))
+        self.step()
+        return terms
+
+    def optimize(self, sample=None):
+        """One eager iteration -> the terms as device scalars (no read-back)."""
+        if sample is not None:
+            self.load(sample)
+        self._use(self._next_row())
+        terms = self._iteration()
+        if "fid" in terms:
+            self.fids.append(terms["fid"])
+        self.t += 1
+        return terms
+
+    def optimize_graphed(self, warmup=2, strict=False):
+        """`optimize()` as one launch: the first `warmup` calls run eagerly (every lazily created buffer, handle and kernel attribute
+        exists afterwards), the next captures the iteration in a HIP graph and every call from then on replays it.  The graph reads
+        PRIVATE static copies of the row; at bs == 1 the next sample is copied into them before each replay (one graph, not two).
+        A failed capture falls back to eager iterations for good, with a warning; `strict` (or env LWG_GRAPH_STRICT=1) re-raises.
+        With a face readout (host-side crops) every call is eager."""
+        import os
+        if self.face is not None or self._graph_failed:
+            return self.optimize()
+        if self._graph is None:
+            if self._graph_warm < warmup:
+                self._graph_warm += 1
+                return self.optimize()
+            row = self._next_row()
+            try:
+                self._static = {k: v.detach().clone() for k, v in row.items()}
+                self._use(self._static)
+                torch.cuda.synchronize()
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                    terms = self._iteration()
+                failed = None
+            except RuntimeError as e:   # what a capture can trip over is reported as RuntimeError (LwgError is one)
+                failed = e
+            if failed is not None:
+                if strict or os.environ.get("LWG_GRAPH_STRICT") == "1":
+                    raise failed
+                import warnings
+                warnings.warn("SwapTuner.optimize_graphed: capture failed (%s: %s); continuing with eager iterations"
+                              % (type(failed).__name__, failed))
+                self._graph_failed, self._static = True, None
+                torch.cuda.synchronize()
+                return self.optimize()
+            self._graph, self._graph_terms = graph, terms
+            self.captures += 1
+        row = self._next_row()
+        if len(self.rows) > 1:
+            for k, v in row.items():
+                self._static[k].copy_(v)
+        self._graph.replay()
+        self.replays += 1
+        self.t += 1
+        return self._graph_terms
+
+    def run(self, graphed=None, on_step=None):
+        """The remaining steps -> `terms_history()`.  `graphed` (default GRAPH) takes `optimize_graphed`; a face readout forces the
+        eager loop.
+        `on_step(step, tuner)` is called after every step (the images of that step are the tuner's attributes)."""
+        graphed = (self.GRAPH if graphed is None else bool(graphed)) and self.face is None
+        while self.t < self.total:
+            step = self.t
+            if graphed:
+                self.optimize_graphed()
+            else:
+                self.optimize()
+            if on_step is not None:
+                on_step(step, self)
+        return self.terms_history()
+
+    def terms_history(self):
+        """The terms of the steps taken so far as floats: one read-back of `history` (and of the fid readouts)."""
+        out = [dict(zip(self.TERMS, r)) for r in self.history[:self.t].cpu().tolist()]
+        if self.fids:
+            for o, f in zip(out, torch.stack(self.fids).cpu().tolist()):
+                o["fid"] = f
+        return out
+
+
+@torch.no_grad()
+def swap_samples(swapper):
+    """The batch Swapper.post_personalize trains on, built on the device from a Swapper after swap_setup: the reference's
+    set_inputs / initialize (models/swapper.py:279-329) in the keys and layout PostTuner.load reads, plus 'bg' (:277).
+
+    Sample 0: src is the source, tsf the target pose; sample 1: the roles exchanged.  Per sample T = cal_bc_transform(source
+    p2verts, target fim, target wim), tsf_img = transform(source img, T), tsf_inputs = cat(tsf_img, target cond), preds =
+    inference(source feats, tsf_inputs, T) blended with the source's bg (through Swapper.warp under --front_warp); T_cycle is T
+    with the rows exchanged; pseudo_masks are the ft_ks erosions of the last channel of src_inputs / tsf_inputs; j2d = [own,
+    other's].  images[:, 1] is the other subject's picture (no loss term reads it)."""
+    a, b = swapper.src_info, swapper.tsf_info
+    if a is None or b is None or 'src_inputs' not in b:
+        raise RuntimeError("swap_samples: swap_setup first")
+    opt, render, gen = swapper._opt, swapper.render, swapper.generator
+
+    def initialize(src, tsf):                                                            # :280-300
+        p2v = src.get('p2verts_c')
+        if p2v is None:
+            p2v = src['p2verts'].float().contiguous()
+        T = render.cal_bc_transform(p2v, tsf['fim'], tsf['wim'])
+        tsf_img = gen.transform(src['img'], T)
+        tsf_inputs = torch.cat([tsf_img, tsf['cond'].float()], dim=1)
+        enc, res = src['feats']
+        preds, _, mask = gen.inference(enc, res, tsf_inputs, T, bg_img=src['bg'])
+        if opt.front_warp:
+            preds = swapper.warp(preds, tsf_img, tsf['fim'], mask)
+        return preds, T, tsf_inputs
+
+    pa, Ta, ia = initialize(a, b)
+    pb, Tb, ib = initialize(b, a)
+    pair = lambda k: torch.cat([a[k], b[k]], dim=0).float()
+    both = lambda t: torch.stack([t, t.flip(0)], dim=1)                                  # [own, other's]
+    T, src_inputs, tsf_inputs, fim = torch.cat([Ta, Tb], dim=0), pair('src_inputs'), torch.cat([ia, ib], dim=0), pair('fim')
+    erode = lambda x: util.morph(x[:, -1:], ks=opt.ft_ks, mode='erode')                  # :324-325
+    return dict(images=both(pair('img')), pseudo_masks=torch.stack([erode(src_inputs), erode(tsf_inputs)], dim=1),
+                j2d=both(pair('j2d')), T=T, T_cycle=T.flip(0).contiguous(), src_inputs=src_inputs, tsf_inputs=tsf_inputs,
+                src_fim=fim, tsf_fim=fim.flip(0).contiguous(), preds=torch.cat([pa, pb], dim=0), bg=pair('bg'))
 
 
 @torch.no_grad()

@@ -34,9 +34,50 @@ class Swapper(Imitator):
         self.part_fn = torch.as_tensor(np.ascontiguousarray(part_fn)).float().contiguous().cuda()
         self.part_faces = [list(p) for p in part_faces]
 
-    def post_personalize(self, *args, **kwargs):
-        raise NotImplementedError("Swapper.post_personalize (swapper.py:273-476: its own loss and learning-rate schedule) is not "
-                                  "built; the Imitator's and the Viewer's is (models/post_tune.py)")
+    def post_personalize(self, out_dir, visualizer, verbose=True):
+        """swapper.py:273-476: adapts the generator to the two subjects of `swap_setup` by 50 cycle fine-tune steps on the batch
+        of the two (models/post_tune.py: SwapTuner, swap_samples), then serves the tuned weights.  `out_dir` is not written to
+        (the reference does not either).  With a visualizer the reference's images are shown every 10th step (:466-471);
+        `verbose` prints the terms once the loop has ended (they stay on the device until then).  The `fid` term is a readout
+        without gradient, computed when `verbose` and a Sphere20a checkpoint exists at `opt.face_model`; it forces the eager
+        loop.  Returns the terms of every step.
+
+        Afterwards, a stated deviation: BOTH subjects' `feats` are re-encoded from their stored `src_inputs` under the tuned
+        weights.  The reference only calls generator.eval() (:476), so its next `swap` reads features the UNTUNED source stream
+        produced and half of the tuning never reaches the picture.  Graphs recorded by `swap_graph` before refuse to replay."""
+        import os
+        from .post_tune import SwapTuner, swap_samples
+        if self.src_info is None or self.tsf_info is None or 'src_inputs' not in self.tsf_info:
+            raise RuntimeError("post_personalize: swap_setup first")
+        opt = self._opt
+        face = None
+        face_model = getattr(opt, 'face_model', '')
+        if verbose and face_model and os.path.isfile(face_model):
+            from ..networks.facenet import SphereFaceLoss
+            face = SphereFaceLoss(torch.load(face_model, map_location='cpu'))
+        sample = swap_samples(self)
+        tuner = SwapTuner(self.generator, sample['bg'], self.render, front_warp=opt.front_warp, face=face, batch_size=opt.batch_size)
+        tuner.load(sample)
+        nchw = lambda t: t.permute(0, 3, 1, 2)
+
+        def show(step, t):                                               # :466-471
+            if visualizer is not None and step % 10 == 0:
+                self.visualize(visualizer, input_imgs=sample['images'][:, 0], tsf_imgs=nchw(t.fake_tsf), cyc_imgs=nchw(t.cyc_tsf),
+                               fake_tsf_mask=nchw(t.t_mask), init_preds=sample['preds'],
+                               str_src_imgs=nchw(t.src_real * (1 - t.src_in[..., 5:6])), cycle_warp_imgs=nchw(t.cyc_warp))
+
+        history = tuner.run(on_step=show)
+        if verbose:
+            for step, terms in enumerate(history):
+                print('step: %d; ' % step + '; '.join('%s: %.6f' % kv for kv in terms.items()))
+        self._serve_tuned(tuner.state_dict())
+        return history
+
+    @torch.no_grad()
+    def _serve_tuned(self, state_dict):
+        """Imitator._serve_tuned (re-encodes src_info['feats']), and the second subject's features as well"""
+        super()._serve_tuned(state_dict)
+        self.tsf_info['feats'] = self.generator.encode_src(self.tsf_info['src_inputs'])
 
     @staticmethod
     def create_meshgrid(image_size):
@@ -157,8 +198,12 @@ class Swapper(Imitator):
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, capture_error_mode="thread_local"):
             preds = self.swap(src_info, tgt_info, target_part)
+        tuned = self._tuned
 
         def run():
+            if self._tuned != tuned:
+                raise RuntimeError("swap_graph: post_personalize changed the weights and the subjects' features since this graph "
+                                   "was recorded; record a new one")
             graph.replay()
             return preds
 

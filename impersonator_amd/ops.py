@@ -269,6 +269,20 @@ def adam_update_device_step(param, grad, exp_avg, exp_avg_sq, step_state, lr, be
                                                        float(eps), _lib.stream_ptr()))
 
 
+def adam_update_scheduled(param, grad, exp_avg, exp_avg_sq, step_state, lr_table, betas=(0.9, 0.999), eps=1e-8):
+    """adam_update_device_step with the learning rate on the device as well: `lr_table` (float32, one rate per step) is read by
+    the kernel at lr_table[min(t, len) - 1] for the advanced count t (include/lwg.h, lwg_adam_update_scheduled) -- a captured
+    iteration replays through a decaying rate without being captured again."""
+    _chk(param, grad, exp_avg, exp_avg_sq, lr_table)
+    if not step_state.is_cuda or step_state.dtype != torch.int64 or step_state.numel() != 3 or not step_state.is_contiguous():
+        raise RuntimeError("adam_update_scheduled: step_state must be adam_step_state(): three int64 words on the device")
+    if lr_table.dim() != 1 or lr_table.numel() < 1:
+        raise RuntimeError("adam_update_scheduled: lr_table must be a non-empty 1-d float32 tensor")
+    _lib.check(_lib.load().lwg_adam_update_scheduled(_lib.ptr(param), _lib.ptr(grad), _lib.ptr(exp_avg), _lib.ptr(exp_avg_sq),
+                                                     param.numel(), _lib.ptr(step_state), _lib.ptr(lr_table), lr_table.numel(),
+                                                     float(betas[0]), float(betas[1]), float(eps), _lib.stream_ptr()))
+
+
 @torch.no_grad()
 def grid_sample_nhwc(x, grid, align_corners=False):
     """F.grid_sample (bilinear, zeros) on NHWC tensors: x (xn,H,W,C) with xn in {1, n}, grid (n,Ho,Wo,2) -> (n,Ho,Wo,C)."""

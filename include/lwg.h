@@ -561,6 +561,13 @@ LWG_API int lwg_adam_update(float *param, const float *grad, float *exp_avg, flo
  * arguments, so a captured HIP graph of a training iteration replays correctly. */
 LWG_API int lwg_adam_update_device_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, size_t n,
                                         void *step_state, float lr, float beta1, float beta2, float eps, lwg_stream_t stream);
+/* The same again with the learning rate in device memory too: the update uses lr = lr_table[min(t, lr_count) - 1], t being the
+ * count AFTER the advance (the first step reads entry 0; steps past the table keep its last entry).  lr_table: lr_count >= 1
+ * floats on the device, read by the kernel when it runs -- neither step nor rate is a launch argument, so ONE captured graph
+ * replays through a whole learning-rate schedule. */
+LWG_API int lwg_adam_update_scheduled(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, size_t n,
+                                      void *step_state, const float *lr_table, int lr_count, float beta1, float beta2, float eps,
+                                      lwg_stream_t stream);
 /* lwg_discriminator_adam_step keeps its step count on the device as well (on != 0; synchronous, call outside a capture, with the
  * betas the following steps will use): see lwg_adam_update_device_step.  Switching it off copies the count back. */
 LWG_API int lwg_discriminator_use_device_step(lwg_discriminator *d, int on, float beta1, float beta2);
