@@ -449,3 +449,235 @@ def heads_bounds(case, precision):
         return ACT_ABS, ACT_ABS
     pre_max = float(case["ref"]["pre"].abs().max())
     return BF16X3_REL * pre_max + ACT_ABS, BF16X3_REL * pre_max / 4 + ACT_ABS
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Order-independent exactness of the bf16x3 (and fp32) convolutions and their gradients: operands on a coarse binary grid.
+# One operand is n / 256 with |n| <= 511 (ten significant bits: it needs its lo term), the other m / 16 with |m| <= 8 (bf16
+# carries it: no lo term, so no lo * lo product is missing from hi*hi + hi*lo + lo*hi).  Every product is a multiple of 2^-12;
+# where the sum of |products| of an output stays below 2^24 quanta, every partial sum in ANY order is an fp32 number and the
+# float64 result rounded to fp32 is the specification, bit for bit.  tests/test_gpu_halo_mfma_shape.py and
+# tests/test_gpu_conv_exact.py hold the kernels to it; tests/test_conv_exact_cases.py proves the conditions and that a wrong
+# hi/lo pairing or tile placement cannot meet it.
+EXACT_FAMILIES = ("a_lo", "b_lo")   # which operand carries the lo term: (activation, weight) forward and data gradient, (x, dy) wgrad
+EXACT_NCU = 256                     # the CU count the CPU statement of the CU-sized batches uses (an MI355X)
+
+
+def grid(shape, g, limit, denom):
+    """integers in [-limit, limit] over denom"""
+    return torch.randint(-limit, limit + 1, shape, generator=g).float() / denom
+
+
+def exact_operands(family, shape_a, shape_b, g):
+    """family 'a_lo': A = n / 256, |n| <= 511, B = m / 16, |m| <= 8; 'b_lo': the converse (A is drawn first in both)"""
+    if family == "a_lo":
+        return grid(shape_a, g, 511, 256.0), grid(shape_b, g, 8, 16.0)
+    assert family == "b_lo"
+    return grid(shape_a, g, 8, 16.0), grid(shape_b, g, 511, 256.0)
+
+
+def bf16_split_f32(t):
+    """fp32 tensor -> (hi, lo) as fp32: hi = bf16(t), lo = bf16(t - hi)"""
+    hi = t.bfloat16().float()
+    lo = (t - hi).bfloat16().float()
+    return hi, lo
+
+
+class ConvCase(object):
+    """One op-level call.  kind 'fwd': operands (x, w) -> y; 'dgrad': (dy, w) -> dx; 'wgrad': (x, dy) -> dW.  H x W is the layer's
+    INPUT map, N a number or a function of the CU count.  axes: per operand, the axis of the channels that the split format
+    groups by 32 (the reduction channels of the forward pass and the data gradient).  pixels: per operand, whether its last axis
+    walks the pixels of a row.  midrow: a 128-pixel tile of the kernel's output starts inside a row and the conv has padding."""
+
+    def __init__(self, kind, cin, cout, k, stride, pad, H, W, N, transposed=False, midrow=False, expect=None, precision="bf16x3"):
+        self.kind, self.cin, self.cout, self.k, self.stride, self.pad = kind, cin, cout, k, stride, pad
+        self.H, self.W, self.N, self.transposed, self.midrow, self.expect, self.precision = H, W, N, transposed, midrow, expect, precision
+
+    def batch(self, ncu):
+        return self.N(ncu) if callable(self.N) else self.N
+
+    def out_hw(self):
+        if self.transposed:
+            return 2 * self.H, 2 * self.W
+        return (self.H + 2 * self.pad - self.k) // self.stride + 1, (self.W + 2 * self.pad - self.k) // self.stride + 1
+
+    def w_shape(self):
+        return (self.cin, self.cout, self.k, self.k) if self.transposed else (self.cout, self.cin, self.k, self.k)
+
+    def shapes(self, ncu):
+        """the two operands' shapes (NCHW / the weight's own layout)"""
+        n, (ho, wo) = self.batch(ncu), self.out_hw()
+        x, dy = (n, self.cin, self.H, self.W), (n, self.cout, ho, wo)
+        return {"fwd": (x, self.w_shape()), "dgrad": (dy, self.w_shape()), "wgrad": (x, dy)}[self.kind]
+
+    @property
+    def axes(self):
+        return {"fwd": (1, 0 if self.transposed else 1), "dgrad": (1, 1 if self.transposed else 0), "wgrad": (1, 1)}[self.kind]
+
+    @property
+    def pixels(self):
+        return (True, self.kind == "wgrad")
+
+    def reduction(self, ncu):
+        """products per output: K of the forward pass / data gradient, pixels of the weight gradient"""
+        ho, wo = self.out_hw()
+        return {"fwd": self.k * self.k * self.cin, "dgrad": self.k * self.k * self.cout, "wgrad": self.batch(ncu) * ho * wo}[self.kind]
+
+    def _conv(self, x, w, wrap_left=False):
+        import torch.nn.functional as F
+        if self.transposed:
+            assert not wrap_left
+            return F.conv_transpose2d(x, w, stride=2, padding=1, output_padding=1)
+        return conv_wrap_left(x, w, self.stride, self.pad) if wrap_left else F.conv2d(x, w, None, self.stride, self.pad)
+
+    def op(self, a, b, wrap_left=False):
+        """The case's bilinear map in float64: F.conv2d / F.conv_transpose2d, or their float64 autograd gradient.  wrap_left
+        (plain convs with padding): the mutant of conv_wrap_left on the conv the kernel runs -- the layer's own forward, or for
+        the stride-1 data gradient the conv of dy with the flipped, transposed filter."""
+        a, b = a.double(), b.double()
+        if self.kind == "fwd":
+            return self._conv(a, b, wrap_left)
+        if self.kind == "dgrad" and wrap_left:
+            assert not self.transposed and self.stride == 1
+            return conv_wrap_left(a, b.flip(2, 3).transpose(0, 1), 1, self.k - 1 - self.pad)
+        assert not wrap_left
+        if self.kind == "dgrad":
+            x = torch.zeros(a.shape[0], self.cin, self.H, self.W, dtype=torch.float64, requires_grad=True)
+            return torch.autograd.grad(self._conv(x, b), x, a)[0]
+        w = torch.zeros(self.w_shape(), dtype=torch.float64, requires_grad=True)
+        return torch.autograd.grad(self._conv(a, w), w, b)[0]
+
+
+def conv_wrap_left(x, w, stride, pad):
+    """F.conv2d whose left padding tap next to column 0 reads the last pixel of the previous row instead of zero (rows 1 and up):
+    what a kernel computes that walks a flat run of pixels and misses a row wrap.  A mutant for the sensitivity checks."""
+    import torch.nn.functional as F
+    assert pad >= 1
+    H, W = x.shape[2:]
+    xp = F.pad(x, (pad, pad, pad, pad))
+    xp[:, :, pad + 1:pad + H, pad - 1] = x[:, :, :H - 1, W - 1]
+    return F.conv2d(xp, w, None, stride, 0)
+
+
+def _every32(t, axis):
+    idx = (torch.arange(t.shape[axis]) % 32 == 0)
+    return idx.view([-1 if d == axis else 1 for d in range(t.dim())])
+
+
+CONV_MUTANTS = ("drop_a_lo", "drop_b_lo", "lo32", "pair32", "wrap_left")
+
+
+def conv_bf16x3(op, a, b, axes=(1, 1), pixels=(True, False), mutant=None):
+    """The split arithmetic of a bilinear map op(A, B) (float64 in, float64 out) restated in float64: hi*hi + lo*hi + hi*lo of
+    the bf16 halves of the fp32 operands a and b (every product exact, sums in float64); a cross product whose lo is zero
+    everywhere is not evaluated.  mutant, each a wrong hi/lo pairing or tile placement:
+      'drop_a_lo' / 'drop_b_lo'  the cross product with that operand's lo left out;
+      'lo32'       lo dropped on every 32nd channel along `axes` (one lane of a 32-channel group of the split format);
+      'pair32'     in each cross product, on every 32nd channel, lo meets the hi of the neighbouring pixel of the row: the
+                   pixel-walking factor (`pixels`; lo where both walk pixels) is shifted by one along its last axis;
+      'wrap_left'  op(..., wrap_left=True) for all three products (conv_wrap_left)."""
+    assert mutant is None or mutant in CONV_MUTANTS
+    (ah, al), (bh, bl) = bf16_split(a), bf16_split(b)
+    kw = dict(wrap_left=True) if mutant == "wrap_left" else {}
+    if mutant == "lo32":
+        al, bl = al.masked_fill(_every32(al, axes[0]), 0.0), bl.masked_fill(_every32(bl, axes[1]), 0.0)
+
+    def pair(lo, hi, lo_axis, hi_axis, lo_pixels, hi_pixels):
+        if mutant != "pair32":
+            return lo, hi
+        assert lo_pixels or hi_pixels
+        if lo_pixels:
+            return torch.where(_every32(lo, lo_axis), lo.roll(1, -1), lo), hi
+        return lo, torch.where(_every32(hi, hi_axis), hi.roll(1, -1), hi)
+
+    y = op(ah, bh, **kw)
+    if mutant != "drop_a_lo" and bool(al.any()):
+        lo, hi = pair(al, bh, axes[0], axes[1], pixels[0], pixels[1])
+        y = y + op(lo, hi, **kw)
+    if mutant != "drop_b_lo" and bool(bl.any()):
+        lo, hi = pair(bl, ah, axes[1], axes[0], pixels[1], pixels[0])
+        y = y + op(hi, lo, **kw)
+    return y
+
+
+def exact_conditions(a, b, op, family):
+    """The conditions under which bit equality is the specification, as a dict of booleans, with the float64 reference: hi + lo
+    carries each operand, the operand without a lo term has none and the other has some, the sum of |products| of every output
+    stays below 2^24 quanta of 2^-12, and the reference is its own fp32 rounding.  Conditions on the inputs, not measurements."""
+    (ah, al), (bh, bl) = bf16_split_f32(a), bf16_split_f32(b)
+    none, some = (bl, al) if family == "a_lo" else (al, bl)
+    ref = op(a, b)
+    return dict(carried=torch.equal(ah + al, a) and torch.equal(bh + bl, b),
+                one_lo=float(none.abs().max()) == 0 and float(some.abs().max()) > 0,
+                quanta=float(op(a.abs(), b.abs()).max()) * 4096 < 2 ** 24,
+                ref_is_fp32=torch.equal(ref.float().double(), ref)), ref
+
+
+def exact_forward_cases():
+    """name -> ConvCase of the forward cases of tests/test_gpu_conv_exact.py: the ring and in-kernel-split rows of
+    tests/test_gpu_conv_dispatch.CASES (one per instantiation, batches sized from the CU count as there) and the shapes whose
+    128-pixel tiles start inside a row."""
+    from tests.test_gpu_conv_dispatch import CASES, _RING, _F32
+    cases = {}
+    for name in ("ring64", "ring128", "ring_tall", "gen64_x3", "gen128_x3", "gen_small_cin_x3"):
+        cin, cout, k, stride, pad, transposed, H, W, n_of, precision = CASES[name]
+        assert precision == "bf16x3" and not transposed
+        cases[name] = ConvCase("fwd", cin, cout, k, stride, pad, H, W, n_of, expect=_RING if name.startswith("ring") else _F32)
+    # 16 x 24 map, 384 pixels: tiles start at row 5 column 8 and at row 10 column 16
+    cases["ring_midrow"] = ConvCase("fwd", 64, 64, 1, 1, 0, 16, 24, 1, expect=_RING)
+    # 16 x 24 output: both horizontal padding taps fall inside tiles, tiles 3 to 5 belong to image 1
+    cases["ring_s2_midrow"] = ConvCase("fwd", 32, 64, 3, 2, 1, 32, 48, 2, midrow=True, expect=_RING)
+    # one 128-pixel tile, K = 2304, 72 stages: many turns of the ring
+    cases["ring_long_k"] = ConvCase("fwd", 256, 64, 3, 2, 1, 16, 32, 1, expect=_RING)
+    return cases
+
+
+def exact_dgrad_cases():
+    """name -> ConvCase of the data-gradient cases, rectangular maps throughout.  lwg_conv2d_backward_data writes dx through
+    64-channel tiles, so the layer's Cin is a multiple of 64: the gradient conv reduces the layer's Cout channels of dy to them."""
+    from tests.test_gpu_conv_dispatch import _HALO, _RING
+    return {
+        # flipped-filter relayout mode 1; a 4 x 32 map is one halo tile
+        "3x3_s1": ConvCase("dgrad", 64, 32, 3, 1, 1, 4, 32, 1, expect=_HALO),
+        # the same at a width that is no multiple of 32: the ring, three tiles per image, padding taps inside tiles
+        "3x3_s1_n3": ConvCase("dgrad", 64, 32, 3, 1, 1, 8, 48, 3, midrow=True, expect=_RING),
+        "1x1": ConvCase("dgrad", 64, 128, 1, 1, 0, 16, 24, 1, expect=_RING),
+        # four-phase transposed conv of dy (4 x 32) behind relayout mode 2
+        "3x3_s2": ConvCase("dgrad", 64, 32, 3, 2, 1, 8, 64, 2, expect=_HALO),
+        # stride-2 ring conv of dy (16 x 32) behind relayout mode 0
+        "conv_transpose": ConvCase("dgrad", 64, 32, 3, 2, 1, 8, 16, 2, transposed=True, expect=_RING),
+    }
+
+
+def exact_wgrad_cases():
+    """name -> ConvCase of the weight-gradient cases: every row of tests/test_gpu_wgrad_dispatch.CASES (expect = its table row),
+    a transposed layer (the roles of x and dy swap), a batch larger than one, and the call whose bias gradient is checked."""
+    from tests.test_gpu_wgrad_dispatch import CASES
+    cases = {}
+    for name, (cin, cout, k, stride, pad, N, H, W, precision, row) in CASES.items():
+        cases[name] = ConvCase("wgrad", cin, cout, k, stride, pad, H, W, N, expect=row, precision=precision)
+    cases["transposed"] = ConvCase("wgrad", 128, 64, 3, 2, 1, 16, 16, 1, transposed=True, expect=2)
+    cases["row3 <64,64> batch 3"] = ConvCase("wgrad", 64, 64, 3, 1, 1, 8, 32, 3, expect=4)
+    cases["bias fp32"] = ConvCase("wgrad", 64, 128, 3, 2, 1, 32, 32, 1, expect=0, precision="fp32")
+    return cases
+
+
+EXACT_KINDS = {"fwd": exact_forward_cases, "dgrad": exact_dgrad_cases, "wgrad": exact_wgrad_cases}
+
+
+@functools.lru_cache(maxsize=None)
+def exact_case_operands(kind, name, family, ncu=EXACT_NCU):
+    """(A, B) of one exact case, seeded by (kind, name, family); family 'random': Gaussian activations, 0.05 x Gaussian second
+    operand.  The 8-channel stem's weight gradient keeps channels 6 and 7 of x at zero.  Shared: treat as read-only."""
+    case = EXACT_KINDS[kind]()[name]
+    families = EXACT_FAMILIES + ("random",)
+    seed = 100000 * sorted(EXACT_KINDS).index(kind) + 10 * sorted(EXACT_KINDS[kind]()).index(name) + families.index(family)
+    g = torch.Generator().manual_seed(seed)
+    sa, sb = case.shapes(ncu)
+    if family == "random":
+        a, b = torch.randn(sa, generator=g), torch.randn(sb, generator=g) * 0.05
+    else:
+        a, b = exact_operands(family, sa, sb, g)
+    if case.cin == 8 and case.kind == "wgrad":
+        a[:, 6:] = 0
+    return a, b

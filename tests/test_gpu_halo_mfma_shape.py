@@ -48,25 +48,22 @@ def _conv64(x, w, transposed):
     return F.conv2d(x.double(), w.double(), None, stride=1, padding=1)
 
 
-def _grid(shape, g, limit, denom):
-    """integers in [-limit, limit] over denom"""
-    return torch.randint(-limit, limit + 1, shape, generator=g).float() / denom
+# the grid families of tests/helpers.py under this file's names: the operands are (x, w)
+_FAMILY = {"x_lo": "a_lo", "w_lo": "b_lo"}
 
 
 @functools.lru_cache(maxsize=None)
 def _operands(case, family):
-    """(x NCHW, w, float64 reference) on the CPU.  family 'x_lo': x = n / 256, |n| <= 511, w = m / 16, |m| <= 8; 'w_lo': the
-    converse; 'random': the operands of tests/test_gpu_ops.py's halo test."""
+    """(x NCHW, w, float64 reference) on the CPU.  family 'x_lo' / 'w_lo': helpers.exact_operands' 'a_lo' / 'b_lo' (x = n / 256,
+    |n| <= 511, w = m / 16, |m| <= 8, and the converse); 'random': the operands of tests/test_gpu_ops.py's halo test."""
     cin, cout, transposed, H, W, n_of = CASES[case]
     N = n_of(_ncu())
     g = torch.Generator().manual_seed(sorted(CASES).index(case) * 10 + ["x_lo", "w_lo", "random"].index(family))
     wshape = (cin, cout, 3, 3) if transposed else (cout, cin, 3, 3)
     if family == "random":
         x, w = torch.randn(N, cin, H, W, generator=g), torch.randn(wshape, generator=g) * 0.05
-    elif family == "x_lo":
-        x, w = _grid((N, cin, H, W), g, 511, 256.0), _grid(wshape, g, 8, 16.0)
     else:
-        x, w = _grid((N, cin, H, W), g, 8, 16.0), _grid(wshape, g, 511, 256.0)
+        x, w = helpers.exact_operands(_FAMILY[family], (N, cin, H, W), wshape, g)
     return x, w, _conv64(x, w, transposed)
 
 
@@ -85,10 +82,7 @@ def _run(case, family):
     return _RUNS[(case, family)][:2]
 
 
-def _split(t):
-    hi = t.bfloat16().float()
-    lo = (t - hi).bfloat16().float()
-    return hi, lo
+_split = helpers.bf16_split_f32
 
 
 @pytest.mark.parametrize("family", ["x_lo", "w_lo"])

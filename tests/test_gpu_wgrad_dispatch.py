@@ -41,14 +41,18 @@ def _ncu():
     return torch.cuda.get_device_properties(0).multi_processor_count
 
 
-def _plan(case):
-    """lwg_wgrad_plan at this device's CU count -> (table row, S, reduction)"""
+def _plan_of(cin, cout, k, stride, pad, N, H, W, precision, transposed=False):
+    """lwg_wgrad_plan of a layer at this device's CU count -> (table row, S, reduction)"""
     from impersonator_amd import _lib, ops
-    cin, cout, k, stride, pad, N, H, W, precision, _ = CASES[case]
-    d = ops._desc((N, H, W, cin), cin, cout, k, stride, pad, False, precision)
+    d = ops._desc((N, H, W, cin), cin, cout, k, stride, pad, transposed, precision)
     info = (ctypes.c_longlong * 10)()
     _lib.check(_lib.load().lwg_wgrad_plan(ctypes.byref(d), 0, _ncu(), info))
     return info[1], info[7], info[9]
+
+
+def _plan(case):
+    """lwg_wgrad_plan of a case at this device's CU count -> (table row, S, reduction)"""
+    return _plan_of(*CASES[case][:9])
 
 
 @functools.lru_cache(maxsize=None)
