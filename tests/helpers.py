@@ -681,3 +681,293 @@ def exact_case_operands(kind, name, family, ncu=EXACT_NCU):
     if case.cin == 8 and case.kind == "wgrad":
         a[:, 6:] = 0
     return a, b
+
+
+# Order-independent exactness of bilinear sampling (csrc/sample.h and its consumers in warp.hip, train.hip, scatter.hip): pixel
+# coordinates on a 1/8-texel lattice make every bilinear weight a multiple of 1/64 in [0, 1]; integer data in [-8, 8] then make every
+# product w * v a multiple of 1/64 of magnitude <= 8, and where 8 * 64 * (longest contribution list) stays below 2^24 every partial
+# sum in ANY order is an fp32 number: the float64 result rounded to fp32 is the specification, bit for bit, for the two forward
+# kernels, the atomic scatter and the planned gather alike.  The grid itself is exact: align_corners=False with power-of-two H, W
+# (g = (2 ix + 1) / W - 1), align_corners=True with power-of-two H - 1, W - 1 (g = 2 ix / (W - 1) - 1), so g and every intermediate
+# of sample.h::unnormalize are fp32 numbers.  tests/test_gpu_sampling_exact.py holds the kernels to it; tests/test_sampling_cases.py
+# proves the conditions and that a wrong unnormalise, floor, validity rule or pitch cannot meet it.
+class SampleCase(object):
+    """One sampling problem: source (xn, C, H, W) with xn in {1, n}, grid (n, Ho, Wo, 2).  kind: 'lattice' (uniform on the lattice
+    over [-2, W + 1] x [-2, H + 1]), 'named' (hand-set border coordinates, then wild values), 'thresholds_exact' /
+    'thresholds_ordered' (list lengths on the plan's thresholds), 'crowded' (every texel queued)."""
+
+    def __init__(self, kind, align, H, W, xn, n, Ho, Wo, seed):
+        self.kind, self.align, self.H, self.W, self.xn, self.n, self.Ho, self.Wo, self.seed = kind, align, H, W, xn, n, Ho, Wo, seed
+
+
+SAMPLE_SIZES = {False: [(8, 16), (16, 4), (1, 2)], True: [(5, 9), (17, 3), (2, 2)]}
+SAMPLE_THRESHOLDS = (1, 2, 31, 32, 33, 63, 64, 65, 255, 256, 257, 4095, 4096, 4097)   # 13 347 pixels: kHeavy, bitonic sizes, kSortMax
+SAMPLE_BLOCKS = [(3 * by, 3 * bx) for by in range(3) for bx in range(5)]              # north-west texels of fifteen 2 x 2 blocks
+SAMPLE_WILD = (float("nan"), float("inf"), -float("inf"), 1e30, -1e30, 3e38, -3e38)
+SAMPLE_POINT = (20.375, 11.625)       # (ix, iy) that the crowded case aims an 80 x 80 patch of image 1 at
+SAMPLE_MUTANTS = ("swap_hw", "other_align", "trunc", "drop_partial", "border_clamp", "last_col", "out_pitch", "first_image_only")
+
+
+def _sample_cases():
+    cases, seed = {}, 0
+    for align in (False, True):
+        for H, W in SAMPLE_SIZES[align]:
+            for xn in (1, 3):
+                seed += 1
+                cases["lattice align %d %dx%d %s" % (align, H, W, "shared" if xn == 1 else "per image")] = \
+                    SampleCase("lattice", align, H, W, xn, 3, 24, 40, seed)
+    # one image on the thresholds cases' dimensions: a second grid for the same plan buffer, and more than one block of pixels
+    cases["lattice align 0 8x16 one image 96x160"] = SampleCase("lattice", False, 8, 16, 1, 1, 96, 160, 40)
+    cases["named align 0"] = SampleCase("named", False, 4, 8, 2, 2, 9, 16, 50)
+    cases["named align 1"] = SampleCase("named", True, 5, 9, 2, 2, 9, 16, 51)
+    cases["thresholds exact"] = SampleCase("thresholds_exact", False, 8, 16, 1, 1, 96, 160, 60)
+    cases["thresholds ordered"] = SampleCase("thresholds_ordered", False, 8, 16, 1, 1, 96, 160, 61)
+    cases["thresholds ordered n3"] = SampleCase("thresholds_ordered", False, 8, 16, 1, 3, 96, 160, 62)
+    cases["crowded"] = SampleCase("crowded", True, 33, 65, 1, 2, 192, 192, 7)
+    return cases
+
+
+SAMPLE_CASES = _sample_cases()
+
+
+def named_coordinates(size):
+    """the border coordinates of the 'named' cases along an axis of `size` texels"""
+    return [-1.5, -1.0, -0.5, -0.125, 0.0, size - 1.0, size - 0.875, size - 0.5, float(size)]
+
+
+def _lattice(g, shape, lo, hi):
+    """float64 multiples of 1/8, uniform on [lo, hi]"""
+    return torch.randint(int(8 * lo), int(8 * hi) + 1, shape, generator=g).double() / 8
+
+
+def sample_pixel_coordinates(case):
+    """(ix, iy, sentinel) of a case: float64 pixel coordinates (n, Ho, Wo) on the 1/8 lattice and the mask of the pixels that carry
+    the -2 sentinel (or, in a 'named' case, a wild value) instead."""
+    g = torch.Generator().manual_seed(case.seed)
+    n, Ho, Wo, H, W = case.n, case.Ho, case.Wo, case.H, case.W
+    shape, P = (n, Ho, Wo), n * Ho * Wo
+    sentinel = torch.zeros(P, dtype=torch.bool)
+    if case.kind == "lattice":
+        ix, iy = _lattice(g, shape, -2, W + 1), _lattice(g, shape, -2, H + 1)
+    elif case.kind == "crowded":
+        ix, iy = _lattice(g, shape, 0, W - 1), _lattice(g, shape, 0, H - 1)
+        ix[1, 50:130, 60:140], iy[1, 50:130, 60:140] = SAMPLE_POINT
+    elif case.kind == "named":
+        xs, ys = named_coordinates(W), named_coordinates(H)
+        ix, iy = torch.full((n, Ho * Wo), 2.5, dtype=torch.float64), torch.full((n, Ho * Wo), 1.5, dtype=torch.float64)
+        ix[:, :81], iy[:, :81] = torch.tensor(xs * 9, dtype=torch.float64), torch.tensor(ys, dtype=torch.float64).repeat_interleave(9)
+        sentinel = sentinel.view(n, -1)
+        sentinel[:, 81:] = True
+        ix[1], iy[1], sentinel[1] = ix[0].flip(0), iy[0].flip(0), sentinel[0].flip(0)   # image 1: image 0's pixels in reverse order
+    else:
+        assert case.kind in ("thresholds_exact", "thresholds_ordered") and not case.align
+        perm = torch.randperm(P, generator=g)
+        ix, iy = torch.zeros(P, dtype=torch.float64), torch.zeros(P, dtype=torch.float64)
+        sentinel[:] = True
+        pos = 0
+        for (ty, tx), K in zip(SAMPLE_BLOCKS, SAMPLE_THRESHOLDS):   # the fifteenth block stays empty
+            pix = perm[pos:pos + K]
+            pos += K
+            inside = _lattice(g, (2, K), 0.125, 0.875) if case.kind == "thresholds_exact" else torch.zeros(2, K, dtype=torch.float64)
+            ix[pix], iy[pix], sentinel[pix] = tx + inside[0], ty + inside[1], False
+    return ix.view(shape), iy.view(shape), sentinel.view(shape)
+
+
+@functools.lru_cache(maxsize=None)
+def sample_grid(case):
+    """The fp32 grid (n, Ho, Wo, 2) of a case, from its pixel coordinates: exact in fp32, as is every intermediate of
+    sample.h::unnormalize.  Sentinel pixels hold -2; in a 'named' case the pixels after the 81 hand-set ones hold SAMPLE_WILD in x
+    only (y inside the image), in y only and in both; image 1 holds image 0's pixels in reverse order.  Shared: read-only."""
+    ix, iy, sentinel = sample_pixel_coordinates(case)
+    norm = (lambda v, s: 2 * v / (s - 1) - 1) if case.align else (lambda v, s: (2 * v + 1) / s - 1)
+    g64 = torch.stack([norm(ix, case.W), norm(iy, case.H)], dim=-1)
+    grid = g64.float()
+    assert torch.equal(grid.double(), g64)
+    if case.kind == "named":
+        wild = torch.tensor(SAMPLE_WILD)
+        tail = grid[0].view(-1, 2)[81:]
+        tail[0:7, 0] = wild
+        tail[7:14, 1] = wild
+        tail[14:63, 0], tail[14:63, 1] = wild.repeat(7), wild.repeat_interleave(7)
+        grid[1] = grid[0].flip(0, 1)
+    else:
+        grid[sentinel] = -2.0
+    return grid
+
+
+def sample_tame(grid):
+    """(grid with every wild entry -- NaN, infinite or of magnitude >= 1e30 -- replaced by -3, mask (n, Ho, Wo) of the pixels that
+    had one): the reference of the 'named' cases is computed from this grid."""
+    wild = ~torch.isfinite(grid) | (grid.abs() >= 1e30)
+    return torch.where(wild, torch.full_like(grid, -3.0), grid), wild.any(-1)
+
+
+@functools.lru_cache(maxsize=None)
+def sample_data(case, C):
+    """(x (xn, C, H, W), dy (n, C, Ho, Wo)): fp32 integers in [-8, 8], seeded by the case and C.  Shared: read-only."""
+    g = torch.Generator().manual_seed(1000 * case.seed + C)
+    draw = lambda *shape: torch.randint(-8, 9, shape, generator=g).float()
+    return draw(case.xn, C, case.H, case.W), draw(case.n, C, case.Ho, case.Wo)
+
+
+@functools.lru_cache(maxsize=None)
+def sample_ordered_dy(case, C=4):
+    """dy (n, C, Ho, Wo) of the 'ordered' family: normal * 2^k, k uniform in [-12, 12] -- an fp32 sum of these depends on its order"""
+    g = torch.Generator().manual_seed(1000 * case.seed + 500 + C)
+    shape = (case.n, C, case.Ho, case.Wo)
+    return torch.randn(shape, generator=g) * torch.pow(2.0, torch.randint(-12, 13, shape, generator=g).float())
+
+
+class SampleTaps(object):
+    """tex (n, Ho, Wo, 4): flat texel index into (xn, H, W) of the taps nw, ne, sw, se, or -1 outside the image; w: their float64
+    weights; valid: tex >= 0; counts (xn * H * W): contributions per texel, zero-weight valid taps included."""
+
+    def __init__(self, tex, w, valid, counts):
+        self.tex, self.w, self.valid, self.counts = tex, w, valid, counts
+
+
+def _sample_taps(grid, H, W, align, xn, mutant=None):
+    assert mutant is None or mutant in SAMPLE_MUTANTS
+    g = grid.double()
+    n, Ho, Wo = g.shape[:3]
+    al = bool(align) != (mutant == "other_align")
+    sx, sy = (H, W) if mutant == "swap_hw" else (W, H)
+    unn = (lambda v, s: (v + 1) / 2 * (s - 1)) if al else (lambda v, s: ((v + 1) * s - 1) / 2)
+    ix, iy = unn(g[..., 0], sx), unn(g[..., 1], sy)
+    # sample.h's clamps: wild coordinates become -4 or size + 4 and sample nothing
+    lo = torch.full_like(ix, -4.0)
+    ix, iy = torch.where(ix > -4, ix, lo).clamp(max=W + 4.0), torch.where(iy > -4, iy, lo).clamp(max=H + 4.0)
+    rnd = torch.trunc if mutant == "trunc" else torch.floor
+    fx, fy = rnd(ix), rnd(iy)
+    ex, ey = fx + 1, fy + 1
+    w = torch.stack([(ex - ix) * (ey - iy), (ix - fx) * (ey - iy), (ex - ix) * (iy - fy), (ix - fx) * (iy - fy)], dim=-1)
+    x0, y0 = fx.long(), fy.long()
+    xs, ys = torch.stack([x0, x0 + 1, x0, x0 + 1], dim=-1), torch.stack([y0, y0, y0 + 1, y0 + 1], dim=-1)
+    valid = (xs >= 0) & (xs < W) & (ys >= 0) & (ys < H)
+    if mutant == "last_col":
+        valid[..., 1::2] &= xs[..., 1::2] < W - 1
+    if mutant == "border_clamp":
+        xs, ys, valid = xs.clamp(0, W - 1), ys.clamp(0, H - 1), torch.ones_like(valid)
+    if mutant == "drop_partial":
+        valid = valid & valid.all(-1, keepdim=True)
+    flat = (ys * Wo + xs) % (H * W) if mutant == "out_pitch" else ys * W + xs
+    base = (torch.arange(n) * (H * W) if xn > 1 else torch.zeros(n, dtype=torch.long)).view(n, 1, 1, 1)
+    tex = torch.where(valid, base + flat, torch.full_like(flat, -1))
+    return SampleTaps(tex, w, valid, torch.bincount(tex[valid], minlength=xn * H * W))
+
+
+def sample_taps(grid, H, W, align, xn):
+    """The four tap texels, weights and validity of every pixel of `grid` on an (xn, H, W) source, in float64 by sample.h's
+    formulas, and the per-texel contribution counts (a valid tap of weight 0 counts, as in gs_plan_count_kernel)."""
+    return _sample_taps(grid, H, W, align, xn)
+
+
+def grid_sample_restated(x, grid, align, mutant=None):
+    """F.grid_sample(x, grid, bilinear, zeros) restated in float64 from sample_taps: x (xn, C, H, W), xn in {1, n} -> (n, C, Ho, Wo).
+    mutant, each a way a kernel goes wrong:
+      'swap_hw'       x unnormalised with H, y with W;
+      'other_align'   the other mode's unnormalise;
+      'trunc'         (int) truncation instead of floor;
+      'drop_partial'  a pixel with any tap outside samples nothing;
+      'border_clamp'  outside taps read the edge texel;
+      'last_col'      east taps valid only for x0 + 1 < W - 1;
+      'out_pitch'     source rows addressed with Wo (wrapped into the image);
+      'first_image_only'  (adjoint, shared source) only image 0's gradient arrives."""
+    assert mutant != "first_image_only"
+    xn, C, H, W = x.shape
+    t = _sample_taps(grid, H, W, align, xn, mutant)
+    xf = x.double().permute(0, 2, 3, 1).reshape(xn * H * W, C)
+    y = torch.zeros(t.tex[..., 0].numel(), C, dtype=torch.float64)
+    for k in range(4):
+        v, idx = t.valid[..., k].reshape(-1, 1), t.tex[..., k].reshape(-1).clamp(min=0)
+        y = y + torch.where(v, t.w[..., k].reshape(-1, 1) * xf[idx], torch.zeros_like(y))
+    return y.view(tuple(grid.shape[:3]) + (C,)).permute(0, 3, 1, 2)
+
+
+def grid_sample_adjoint_restated(dy, grid, x_shape, align, mutant=None):
+    """The input gradient of grid_sample_restated: dy (n, C, Ho, Wo) -> dx of x_shape (xn, C, H, W), float64."""
+    xn, C, H, W = x_shape
+    t = _sample_taps(grid, H, W, align, xn, None if mutant == "first_image_only" else mutant)
+    dyf = dy.double().permute(0, 2, 3, 1).reshape(-1, C).clone()
+    if mutant == "first_image_only":
+        assert xn == 1
+        dyf[dy.shape[2] * dy.shape[3]:] = 0
+    dx = torch.zeros(xn * H * W, C, dtype=torch.float64)
+    for k in range(4):
+        v = t.valid[..., k].reshape(-1)
+        dx.index_add_(0, t.tex[..., k].reshape(-1)[v], (t.w[..., k].reshape(-1, 1) * dyf)[v])
+    return dx.view(xn, H, W, C).permute(0, 3, 1, 2)
+
+
+def grid_sample_float64(x, grid, align, dy):
+    """(y, dx): F.grid_sample and its input gradient for the cotangent dy, float64 on the CPU -- the reference"""
+    import torch.nn.functional as F
+    xr = x.double().clone().requires_grad_(True)
+    n = grid.shape[0]
+    y = F.grid_sample(xr.expand(n, -1, -1, -1) if x.shape[0] == 1 and n > 1 else xr, grid.double(), mode="bilinear",
+                      padding_mode="zeros", align_corners=bool(align))
+    y.backward(dy.double())
+    return y.detach(), xr.grad
+
+
+def sample_case_mutants(case):
+    """The mutants that must change a case's result, from its geometry: a square source hides swap_hw; a one-row source or
+    Wo == W hides out_pitch; coordinates inside the image hide trunc; the threshold blocks have every tap inside and never reach
+    the last column, nor does an east tap of the named coordinates; in the crowded case an outside tap has weight 0 (ix = W - 1 exactly), which border_clamp keeps at nothing."""
+    inside = case.kind in ("thresholds_exact", "thresholds_ordered", "crowded")
+    m = ["other_align"]
+    if case.H != case.W:
+        m.append("swap_hw")
+    if not inside:
+        m.append("trunc")
+    if not case.kind.startswith("thresholds"):
+        m.append("drop_partial")
+    if case.kind in ("lattice", "crowded"):   # no named coordinate has x0 = W - 2
+        m.append("last_col")
+    if case.kind != "crowded":
+        m.append("border_clamp")
+    if case.H > 1 and case.Wo != case.W:
+        m.append("out_pitch")
+    if case.xn == 1 and case.n > 1:
+        m.append("first_image_only")
+    return m
+
+
+def sample_threshold_lists(case, taps):
+    """[(K, texel, pixels)] of a thresholds case: the aimed (north-west) texel of every used block and the flat indices of the
+    pixels aiming at it, ascending -- the key order of its contribution list."""
+    nw = taps.tex[..., 0].reshape(-1)
+    return [(K, ty * case.W + tx, torch.nonzero(nw == ty * case.W + tx).reshape(-1))
+            for (ty, tx), K in zip(SAMPLE_BLOCKS, SAMPLE_THRESHOLDS)]
+
+
+def ordered_running_sums(dy, lists, T, reverse=False):
+    """dx (T, C) fp32 of the 'ordered' family: the aimed texel of each list gets the numpy float32 running sum of its pixels' dy
+    (n, C, Ho, Wo) in ascending pixel index -- what acc = fma(1, dy, acc) in key order computes; every other texel 0."""
+    rows = dy.permute(0, 2, 3, 1).reshape(-1, dy.shape[1]).numpy()
+    dx = np.zeros((T, rows.shape[1]), dtype=np.float32)
+    for _, tex, pixels in lists:
+        acc = np.zeros(rows.shape[1], dtype=np.float32)
+        for p in (reversed(pixels.tolist()) if reverse else pixels.tolist()):
+            acc = acc + rows[p]
+        dx[tex] = acc
+    return torch.from_numpy(dx)
+
+
+SAMPLE_FLOW_SIZES = [(17, 9), (9, 5), (65, 33), (33, 17), (3, 2), (1, 1)]
+
+
+@functools.lru_cache(maxsize=None)
+def sample_flow():
+    """A dyadic flow (2, 33, 17, 2): multiples of 1/64 in [-2, 1] with a patch of the -2 sentinel.  Every scale 32 / (h - 1),
+    16 / (w - 1) of SAMPLE_FLOW_SIZES is a power of two, so the interpolation weights are dyadic and fp32 is exact."""
+    g = torch.Generator().manual_seed(33)
+    T = torch.randint(-128, 65, (2, 33, 17, 2), generator=g).float() / 64
+    T[0, 5:12, 3:9] = -2.0
+    return T
+
+
+def resize_flow_float64(T, h, w):
+    """F.interpolate(bilinear, align_corners=True) of a flow (bs, H, W, 2) to (bs, h, w, 2), float64"""
+    import torch.nn.functional as F
+    return F.interpolate(T.double().permute(0, 3, 1, 2), size=(h, w), mode="bilinear", align_corners=True).permute(0, 2, 3, 1).contiguous()

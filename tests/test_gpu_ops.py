@@ -235,54 +235,61 @@ def test_instance_norm_forward_backward(relu, H):
     assert _rel(dg.cpu(), gr.grad) < 2e-5 and _rel(db.cpu(), br.grad) < 2e-5
 
 
+_ALIGN = pytest.mark.parametrize("align", [False, True], ids=["align0", "align1"])
+
+
+@pytest.mark.parametrize("H,W", [(20, 20), (20, 28)], ids=["square", "rect"])
+@_ALIGN
 @pytest.mark.parametrize("shared", [False, True])
-def test_grid_sample_backward(shared):
+def test_grid_sample_backward(shared, align, H, W):
     from impersonator_amd import ops
     g = torch.Generator().manual_seed(12)
-    n, C, H = 3, 64, 20
-    x = torch.randn(1 if shared else n, C, H, H, generator=g)
-    grid = torch.rand(n, H, H, 2, generator=g) * 2.6 - 1.3
+    n, C = 3, 64
+    x = torch.randn(1 if shared else n, C, H, W, generator=g)
+    grid = torch.rand(n, H, W, 2, generator=g) * 2.6 - 1.3
     grid[0, 5:9, 3:8] = -2
-    dy = torch.randn(n, C, H, H, generator=g)
+    dy = torch.randn(n, C, H, W, generator=g)
     xr = x.clone().requires_grad_(True)
-    F.grid_sample(xr.expand(n, -1, -1, -1) if shared else xr, grid, align_corners=False).backward(dy)
-    dx = ops.grid_sample_backward(dy.permute(0, 2, 3, 1).contiguous().cuda(), grid.cuda(), (x.shape[0], H, H, C), False)
+    F.grid_sample(xr.expand(n, -1, -1, -1) if shared else xr, grid, align_corners=align).backward(dy)
+    dx = ops.grid_sample_backward(dy.permute(0, 2, 3, 1).contiguous().cuda(), grid.cuda(), (x.shape[0], H, W, C), align)
     assert _rel(dx.cpu().permute(0, 3, 1, 2), xr.grad) < 1e-5
 
 
+@pytest.mark.parametrize("H,W,Ho,Wo", [(16, 16, 48, 48), (20, 28, 20, 28)], ids=["square", "rect"])
+@_ALIGN
 @pytest.mark.parametrize("shared", [False, True])
-def test_grid_sample_backward_is_bit_reproducible_also_on_crowded_texels(shared):
+def test_grid_sample_backward_is_bit_reproducible_also_on_crowded_texels(shared, align, H, W, Ho, Wo):
     """The deterministic gradient (csrc/scatter.hip: per-texel contribution lists in pixel order, gathered): identical bits run
     after run where the atomic scatter is not, also when a whole image samples ONE location (lists of 48 x 48 entries: the
-    dense-scan path) and when a 3x magnification packs ~9 pixels per texel (the per-thread sort path); one plan serves several
-    tensors; values against float64 autograd."""
+    LDS-sorted path) and when a 3x magnification packs ~9 pixels per texel (the per-thread sort path); one plan serves several
+    tensors; values against float64 autograd.  Both align modes; the rectangular case is a 20 x 28 source under a 20 x 28 grid."""
     from impersonator_amd import ops
     g = torch.Generator().manual_seed(21)
-    n, C, H, Ho = 3, 32, 16, 48
-    x = torch.randn(1 if shared else n, C, H, H, generator=g)
-    grid = (torch.rand(n, Ho, Ho, 2, generator=g) * 2 - 1) * 0.33           # every output pixel lands in the central third
-    grid[1] = torch.tensor([0.113, -0.271])                                   # image 1: one location for all 2304 pixels
-    grid[2, :, :24] = -2                                                      # sentinel half: samples nothing
-    dy = torch.randn(n, C, Ho, Ho, generator=g)
+    n, C = 3, 32
+    x = torch.randn(1 if shared else n, C, H, W, generator=g)
+    grid = (torch.rand(n, Ho, Wo, 2, generator=g) * 2 - 1) * 0.33           # every output pixel lands in the central third
+    grid[1] = torch.tensor([0.113, -0.271])                                   # image 1: one location for all its pixels
+    grid[2, :, :Wo // 2] = -2                                                 # sentinel half: samples nothing
+    dy = torch.randn(n, C, Ho, Wo, generator=g)
     xr = x.double().clone().requires_grad_(True)
-    F.grid_sample(xr.expand(n, -1, -1, -1) if shared else xr, grid.double(), align_corners=False).backward(dy.double())
+    F.grid_sample(xr.expand(n, -1, -1, -1) if shared else xr, grid.double(), align_corners=align).backward(dy.double())
     dyd, gd = dy.permute(0, 2, 3, 1).contiguous().cuda(), grid.cuda()
-    shape = (x.shape[0], H, H, C)
-    plan = ops.GridSamplePlan(gd, shape, False)
-    runs = [ops.grid_sample_backward(dyd, gd, shape, False, plan=plan) for _ in range(3)]
-    runs.append(ops.grid_sample_backward(dyd, gd, shape, False))              # a plan of its own
+    shape = (x.shape[0], H, W, C)
+    plan = ops.GridSamplePlan(gd, shape, align)
+    runs = [ops.grid_sample_backward(dyd, gd, shape, align, plan=plan) for _ in range(3)]
+    runs.append(ops.grid_sample_backward(dyd, gd, shape, align))              # a plan of its own
     torch.cuda.synchronize()
     assert all(torch.equal(r, runs[0]) for r in runs[1:])
     assert _rel(runs[0].cpu().permute(0, 3, 1, 2).double(), xr.grad) < 2e-6
-    atomic = ops.grid_sample_backward(dyd, gd, shape, False, deterministic=False)
+    atomic = ops.grid_sample_backward(dyd, gd, shape, align, deterministic=False)
     assert _rel(atomic.cpu().permute(0, 3, 1, 2).double(), xr.grad) < 1e-5
     # the same plan, another channel count
-    dy2 = torch.randn(n, Ho, Ho, 8, generator=g)
-    a = ops.grid_sample_backward(dy2.cuda(), gd, (x.shape[0], H, H, 8), False, plan=plan)
-    b = ops.grid_sample_backward(dy2.cuda(), gd, (x.shape[0], H, H, 8), False, deterministic=False)
+    dy2 = torch.randn(n, Ho, Wo, 8, generator=g)
+    a = ops.grid_sample_backward(dy2.cuda(), gd, (x.shape[0], H, W, 8), align, plan=plan)
+    b = ops.grid_sample_backward(dy2.cuda(), gd, (x.shape[0], H, W, 8), align, deterministic=False)
     assert float((a - b).abs().max()) <= 1e-3 * float(b.abs().max())
     with pytest.raises(ValueError):
-        ops.grid_sample_backward(dyd, gd, (x.shape[0], H + 1, H, C), False, plan=plan)
+        ops.grid_sample_backward(dyd, gd, (x.shape[0], H + 1, W, C), align, plan=plan)
 
 
 def test_grid_sample_backward_minifying_flow_takes_the_sorted_lists_and_stays_fast():
@@ -334,16 +341,18 @@ def test_adam_update():
     assert float((pg.cpu() - ref.detach()).abs().max()) < 1e-6
 
 
-def test_grid_sample_nhwc_forward():
+@pytest.mark.parametrize("H,W,Ho,Wo", [(20, 20, 12, 12), (20, 28, 12, 36)], ids=["square", "rect"])
+@_ALIGN
+def test_grid_sample_nhwc_forward(align, H, W, Ho, Wo):
     from impersonator_amd import ops
     g = torch.Generator().manual_seed(14)
-    x = torch.randn(3, 64, 20, 20, generator=g)
-    grid = torch.rand(3, 12, 12, 2, generator=g) * 2.6 - 1.3
-    ref = F.grid_sample(x, grid, align_corners=False)
-    y = ops.grid_sample_nhwc(x.permute(0, 2, 3, 1).contiguous().cuda(), grid.cuda())
+    x = torch.randn(3, 64, H, W, generator=g)
+    grid = torch.rand(3, Ho, Wo, 2, generator=g) * 2.6 - 1.3
+    ref = F.grid_sample(x, grid, align_corners=align)
+    y = ops.grid_sample_nhwc(x.permute(0, 2, 3, 1).contiguous().cuda(), grid.cuda(), align)
     assert _rel(y.cpu().permute(0, 3, 1, 2), ref) < 1e-5
-    y1 = ops.grid_sample_nhwc(x[:1].permute(0, 2, 3, 1).contiguous().cuda(), grid.cuda())
-    assert _rel(y1.cpu().permute(0, 3, 1, 2), F.grid_sample(x[:1].expand(3, -1, -1, -1), grid, align_corners=False)) < 1e-5
+    y1 = ops.grid_sample_nhwc(x[:1].permute(0, 2, 3, 1).contiguous().cuda(), grid.cuda(), align)
+    assert _rel(y1.cpu().permute(0, 3, 1, 2), F.grid_sample(x[:1].expand(3, -1, -1, -1), grid, align_corners=align)) < 1e-5
 
 
 _WGRAD_PROBE = r"""
