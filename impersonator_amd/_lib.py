@@ -104,6 +104,10 @@ _PROTOS = {
     "lwg_stem_forward": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _vp]),
     "lwg_heads_inference_workspace_bytes": (_c.c_size_t, [_i, _i, _i]),
     "lwg_heads_inference": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _c.c_size_t, _vp]),
+    "lwg_norm_conv_workspace_bytes": (_c.c_size_t, [_vp]),
+    "lwg_norm_conv_forward": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _c.POINTER(_i), _vp, _c.c_size_t, _vp]),
+    "lwg_norm_finalize": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _f, _vp, _vp]),
+    "lwg_norm_apply": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp]),
     "lwg_discriminator_input_grad": (_i, [_vp, _vp, _i, _c.c_float, _vp, _vp, _vp]),
     "lwg_discriminator_backward_scaled": (_i, [_vp, _vp, _vp, _i, _c.c_float, _vp, _vp]),
     "lwg_discriminator_input_grad_scaled": (_i, [_vp, _vp, _i, _c.c_float, _c.c_float, _vp, _vp, _vp]),

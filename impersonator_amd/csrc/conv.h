@@ -95,6 +95,8 @@ enum { kIgemmReg64 = 0, kIgemmReg128 = 1, kIgemmSmallCin = 2, kIgemmDma64 = 3, k
        kIgemmBf16x3_128 = 6, kDirectStemBf16x3 = 7, kHaloBf16x3_128 = 8, kHaloBf16x3_64 = 9, kIgemmDma32 = 10, kIgemmVariants = 11 };
 extern const char *const kIgemmVariantNames[kIgemmVariants];
 int launch_conv_igemm(const ConvArgs &a, int bn, hipStream_t st, int *variant = nullptr);
+// every refusal launch_conv_igemm(a, bn) would answer with, without launching anything (LWG_OK: it would run)
+int check_conv_igemm(const ConvArgs &a, int bn);
 // true when launch_conv_igemm(a, bn) would run a kernel that honours a.raw_in (the halo-resident 3x3 / transposed kernels)
 bool conv_raw_input_supported(const ConvArgs &a, int bn);
 
@@ -133,7 +135,9 @@ struct ApplyArgs {
     const float *warp_T[2];         // flow resized to (N,H,W,2)
     int align_corners;
 };
-int launch_apply(const ApplyArgs &a, hipStream_t st);
+// lanes (diagnostic entry lwg_norm_apply): 0 = the launcher's choice (apply8_kernel for split buffers unless LWG_APPLY8=0), 4 forces
+// apply_kernel, 8 forces apply8_kernel (split only)
+int launch_apply(const ApplyArgs &a, hipStream_t st, int lanes = 0);
 
 // in-place split-bf16 -> fp32 of n floats (n % 32 == 0): the test hook's view of a split activation buffer
 int launch_unsplit(float *buf, size_t n, hipStream_t st);

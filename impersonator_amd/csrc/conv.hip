@@ -2193,6 +2193,12 @@ static int plan_conv_igemm(const ConvArgs &a, int bn, int ncu, const ConvSwitche
     return choose(kF32_64 + tile, grid, reg_lds(bn));
 }
 
+int check_conv_igemm(const ConvArgs &a, int bn)
+{
+    ConvLaunch L;
+    return plan_conv_igemm(a, bn, device_cu_count(), conv_switches(), false, 0, &L);
+}
+
 int launch_conv_igemm(const ConvArgs &a_in, int bn, hipStream_t st, int *variant)
 {
     ConvArgs a = a_in;   // (a traced launch attaches its record block)
@@ -2299,15 +2305,17 @@ int launch_in_finalize(const float2 *partials, int nphase, int mtiles, int N, in
     return LWG_OK;
 }
 
-int launch_apply(const ApplyArgs &a, hipStream_t st)
+int launch_apply(const ApplyArgs &a, hipStream_t st, int lanes)
 {
+    if (lanes != 0 && lanes != 4 && lanes != 8) LWG_FAIL(LWG_ERR_INVALID_ARG, "apply: lanes=%d (0: the launcher's choice, 4, 8)", lanes);
+    if (lanes == 8 && !a.split) LWG_FAIL(LWG_ERR_UNSUPPORTED, "apply: eight channels per thread is the split-bf16 kernel");
     if ((a.C & 3) || (a.ld_dst & 3) || (a.res && (a.ld_res & 3)))
         LWG_FAIL(LWG_ERR_UNSUPPORTED, "apply: channel counts/strides must be multiples of 4 (C=%d)", a.C);
     if (a.split && ((a.C & 31) || (a.ld_dst & 31) || ((uintptr_t)a.dst & 127) ||
                     (a.res && ((a.ld_res & 31) || ((uintptr_t)a.res & 127)))))
         LWG_FAIL(LWG_ERR_UNSUPPORTED, "apply: split-bf16 buffers need 32-channel granularity (C=%d)", a.C);
     static const char *a8_env = getenv("LWG_APPLY8");   // "0": four channels per thread everywhere (A/B switch)
-    if (a.split && !(a8_env && a8_env[0] == '0')) {
+    if (lanes == 8 || (lanes == 0 && a.split && !(a8_env && a8_env[0] == '0'))) {
         const long total8 = (long)a.N * a.H * a.W * (a.C >> 3);
         apply8_kernel<<<ceil_div(total8, 256), 256, 0, st>>>(a);
         LWG_LAUNCH_CHECK("apply8_kernel");

@@ -2937,6 +2937,187 @@ int lwg_heads_inference(const float *x, int N, int H, int W, const float *scale_
     return launch_heads_bf16x3(h, wfrag, st, bands);
 }
 
+// Diagnostic entries (include/lwg.h): the inference path's norm chain link by link -- a conv with its statistics epilogue as run_conv
+// (generator.hip) launches it, in_finalize, apply -- on caller-supplied tensors.
+namespace {
+// the tile width conv_args (generator.hip) picks for a layer of this shape; fuse as it sets ConvArgs::fuse_phases
+int norm_conv_tile(const lwg_conv2d_desc *d, int mtiles, int nphase, int *fuse)
+{
+    *fuse = 0;
+    if (d->transposed) {
+        if (d->precision == 1 && d->Cout % 128 == 0) return 128;
+        *fuse = 1;
+        return 64;
+    }
+    const long tiles128 = (long)mtiles * (d->Cout / 128) * nphase;
+    int bn = (d->Cout % 128 == 0 && tiles128 >= 256) ? 128 : 64;
+    static const char *bn32_env = getenv("LWG_F32_BN32");
+    if (bn == 64 && d->precision == 0 && d->Cin >= kConvBK && d->k * d->k <= 32 && d->Cout % 32 == 0 &&
+        (long)mtiles * (d->Cout / 64) * nphase * 2 <= 256 && !(bn32_env && bn32_env[0] == '0'))
+        bn = 32;
+    return bn;
+}
+// the workspace is lwg_conv2d_forward's bf16x3 one whatever the precision: the zero run behind the operand serves both
+lwg_conv2d_desc norm_conv_ws_desc(const lwg_conv2d_desc *d)
+{
+    lwg_conv2d_desc w = *d;
+    w.precision = 1;
+    return w;
+}
+}  // namespace
+
+size_t lwg_norm_conv_workspace_bytes(const lwg_conv2d_desc *d)
+{
+    if (!d) return 0;
+    const lwg_conv2d_desc w = norm_conv_ws_desc(d);
+    return lwg_conv2d_workspace_bytes(&w);
+}
+
+int lwg_norm_conv_forward(const lwg_conv2d_desc *d, const float *x, const float *w, int bn, const float *in_scale_shift,
+                          int raw_from, float *y, float *partials, int *variant_host, void *ws, size_t ws_bytes,
+                          lwg_stream_t stream)
+{
+    ConvGeom g;
+    int rc = conv_geom(d, &g);
+    if (rc != LWG_OK) return rc;
+    LWG_REQUIRE(x && w && y && partials && ws, "norm_conv_forward: NULL argument");
+    LWG_REQUIRE(d->precision == 0 || d->precision == 1, "norm_conv_forward: precision=%d (0: fp32, 1: bf16x3)", d->precision);
+    LWG_REQUIRE(bn == 0 || bn == 32 || bn == 64 || bn == 128, "norm_conv_forward: bn=%d (0: the generator's rule, 32, 64, 128)", bn);
+    LWG_REQUIRE(((uintptr_t)x | (uintptr_t)w | (uintptr_t)y) % 16 == 0 && (uintptr_t)partials % 8 == 0,
+                "norm_conv_forward: x, w and y must be 16-byte aligned (partials 8)");
+    LWG_REQUIRE(!in_scale_shift || (uintptr_t)in_scale_shift % 8 == 0, "norm_conv_forward: in_scale_shift must be 8-byte aligned");
+    LWG_REQUIRE((uintptr_t)ws % 16 == 0 && d->pad >= 0, "norm_conv_forward: the workspace must be 16-byte aligned, pad >= 0");
+    if (in_scale_shift && d->precision != 1)
+        LWG_FAIL(LWG_ERR_UNSUPPORTED, "norm_conv_forward: raw input is taken by the bf16x3 halo kernels only");
+    {
+        const lwg_conv2d_desc wd = norm_conv_ws_desc(d);
+        const size_t need = lwg_conv2d_workspace_bytes(&wd);
+        if (ws_bytes < need) LWG_FAIL(LWG_ERR_WORKSPACE, "norm_conv_forward: workspace of %zu bytes, %zu needed", ws_bytes, need);
+    }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const SplitWs sw = carve_split(d, g, ws);
+    const bool split = d->precision == 1;
+    float *wm = split ? sw.w : static_cast<float *>(ws);
+
+    ConvArgs a = base_args(x, d->Cin, d->N, d->H, d->Cin, wm, y, d->Cout);
+    a.W = d->W;
+    a.general = 0;
+    a.tap_inner = 1;
+    a.dil = 1;
+    a.zeros = sw.zeros;
+    a.partials = reinterpret_cast<float2 *>(partials);
+    if (d->transposed) {
+        a.Hm = d->H; a.Wm = d->W; a.Ho = 2 * d->H; a.Wo = 2 * d->W;
+        a.stride = 1; a.pad = 0; a.os = 2;
+        a.nphase = 4;
+        long off = 0;
+        for (int p = 0; p < 4; ++p) {   // the phase matrices relayout (mode 2) writes: op_convT
+            const int py = p >> 1, px = p & 1, nt = (1 + py) * (1 + px);
+            a.ph[p] = ConvPhase{1 + py, 1 + px, nt, nt * d->Cin, off, py, px, 0, 0};
+            off += (long)d->Cout * nt * d->Cin;
+        }
+    } else {
+        a.Hm = a.Ho = g.Ho; a.Wm = a.Wo = g.Wo;
+        a.stride = d->stride; a.pad = d->pad; a.os = 1;
+        a.nphase = 1;
+        a.ph[0] = ConvPhase{d->k, d->k, d->k * d->k, (int)align_up((size_t)d->k * d->k * d->Cin, kConvBK), 0, 0, 0, 0, 0};
+    }
+    if (((long)d->N * a.Hm * a.Wm) % kConvBM)
+        LWG_FAIL(LWG_ERR_UNSUPPORTED, "norm_conv_forward: %d x %dx%d output pixels are not whole 128-pixel tiles", d->N, a.Hm, a.Wm);
+    a.mtiles = d->N * a.Hm * a.Wm / kConvBM;
+    int fuse = 0;
+    const int bn_rule = norm_conv_tile(d, a.mtiles, a.nphase, &fuse);
+    a.fuse_phases = fuse;
+    if (bn == 0) bn = bn_rule;
+    if (split) {
+        if (d->Cin % 32) LWG_FAIL(LWG_ERR_UNSUPPORTED, "norm_conv_forward: the bf16x3 path needs Cin %% 32 == 0, got %d", d->Cin);
+        a.x = sw.x;
+        a.w_split = sw.w;
+        a.precision = 1;
+    }
+    if (in_scale_shift) {
+        a.raw_in = 1;
+        a.raw_from = raw_from;
+        a.in_ss = reinterpret_cast<const float2 *>(in_scale_shift);
+        a.in_ss_ld = d->Cin - raw_from;
+    }
+    if ((rc = check_conv_igemm(a, bn)) != LWG_OK) return rc;   // every refusal of the dispatcher, before the first launch
+
+    const size_t x_floats = (size_t)d->N * d->H * d->W * d->Cin;
+    if (d->transposed) {
+        if ((rc = relayout(w, wm, 2, d->Cin, d->Cout, 9, (long)g.w_floats, st, 0, split)) != LWG_OK) return rc;
+    } else if ((rc = relayout(w, wm, 0, d->Cout, d->Cin, d->k * d->k, (long)g.w_floats, st, a.ph[0].Kpad, split)) != LWG_OK) {
+        return rc;
+    }
+    if (split) {
+        if ((rc = split_pack(x, sw.x, x_floats, st, sw.zeros, sw.zero_floats)) != LWG_OK) return rc;
+        if (in_scale_shift)   // channels >= raw_from stay as the producer wrote them: raw fp32 over the split copy
+            LWG_HIP(hipMemcpy2DAsync(sw.x + raw_from, (size_t)d->Cin * sizeof(float), x + raw_from, (size_t)d->Cin * sizeof(float),
+                                     (size_t)(d->Cin - raw_from) * sizeof(float), (size_t)d->N * d->H * d->W,
+                                     hipMemcpyDeviceToDevice, st));
+    } else {
+        LWG_HIP(hipMemsetAsync(sw.zeros, 0, sw.zero_floats * sizeof(float), st));
+    }
+    int variant = -1;
+    if ((rc = launch_conv_igemm(a, bn, st, &variant)) != LWG_OK) return rc;
+    if (variant_host) *variant_host = variant;
+    return LWG_OK;
+}
+
+int lwg_norm_finalize(const float *partials, int nphase, int mtiles, int N, int C, const float *gamma, const float *beta, float eps,
+                      float *scale_shift, lwg_stream_t stream)
+{
+    LWG_REQUIRE(partials && gamma && beta && scale_shift, "norm_finalize: NULL argument");
+    LWG_REQUIRE(nphase >= 1 && nphase <= 4 && mtiles >= 1 && N >= 1 && C >= 1,
+                "norm_finalize: bad sizes (nphase=%d, mtiles=%d, N=%d, C=%d)", nphase, mtiles, N, C);
+    LWG_REQUIRE(eps >= 0.f, "norm_finalize: eps=%g", (double)eps);
+    LWG_REQUIRE(((uintptr_t)partials | (uintptr_t)scale_shift) % 8 == 0 && ((uintptr_t)gamma | (uintptr_t)beta) % 4 == 0,
+                "norm_finalize: partials and scale_shift must be 8-byte aligned");
+    if (mtiles % N) LWG_FAIL(LWG_ERR_UNSUPPORTED, "norm_finalize: %d tiles do not split over %d images", mtiles, N);
+    if (N > 65535) LWG_FAIL(LWG_ERR_UNSUPPORTED, "norm_finalize: N=%d above the grid's 65535", N);
+    return launch_in_finalize(reinterpret_cast<const float2 *>(partials), nphase, mtiles, N, C, gamma, beta, eps,
+                              reinterpret_cast<float2 *>(scale_shift), reinterpret_cast<hipStream_t>(stream));
+}
+
+int lwg_norm_apply(const float *raw, int N, int H, int W, int C, const float *scale_shift, int relu, float *dst, int ld_dst,
+                   const float *res, int ld_res, int split, int nwarp, const float *warp_src0, int warp_n0, const float *warp_T0,
+                   const float *warp_src1, int warp_n1, const float *warp_T1, int align_corners, int lanes, lwg_stream_t stream)
+{
+    LWG_REQUIRE(raw && scale_shift && dst, "norm_apply: NULL argument");
+    LWG_REQUIRE(N >= 1 && H >= 1 && W >= 1 && C >= 4, "norm_apply: bad sizes (N=%d, H=%d, W=%d, C=%d)", N, H, W, C);
+    LWG_REQUIRE(nwarp >= 0 && nwarp <= 2, "norm_apply: nwarp=%d (0..2)", nwarp);
+    LWG_REQUIRE(lanes == 0 || lanes == 4 || lanes == 8, "norm_apply: lanes=%d (0: the launcher's choice, 4, 8)", lanes);
+    LWG_REQUIRE((split == 0 || split == 1) && (relu == 0 || relu == 1) && (align_corners == 0 || align_corners == 1),
+                "norm_apply: split, relu and align_corners are 0 or 1");
+    LWG_REQUIRE(ld_dst >= C && (!res || ld_res >= C), "norm_apply: pixel strides below C=%d (ld_dst=%d, ld_res=%d)", C, ld_dst, ld_res);
+    const float *wsrc[2] = {warp_src0, warp_src1}, *wT[2] = {warp_T0, warp_T1};
+    const int wn[2] = {warp_n0, warp_n1};
+    for (int k = 0; k < nwarp; ++k) {
+        LWG_REQUIRE(wsrc[k] && wT[k], "norm_apply: NULL warp term %d", k);
+        LWG_REQUIRE(wn[k] == 1 || wn[k] == N, "norm_apply: warp_n%d=%d, must be 1 or the batch size %d", k, wn[k], N);
+        LWG_REQUIRE((uintptr_t)wsrc[k] % 16 == 0 && (uintptr_t)wT[k] % 8 == 0, "norm_apply: warp term %d is not 16 / 8-byte aligned", k);
+    }
+    LWG_REQUIRE(((uintptr_t)raw | (uintptr_t)scale_shift | (uintptr_t)dst | (uintptr_t)res) % 16 == 0,
+                "norm_apply: raw, scale_shift, dst and res must be 16-byte aligned");
+    if ((C & 3) || (ld_dst & 3) || (res && (ld_res & 3)))
+        LWG_FAIL(LWG_ERR_UNSUPPORTED, "norm_apply: channel counts / strides must be multiples of 4 (C=%d)", C);
+    if (split && ((C & 31) || (ld_dst & 31) || ((uintptr_t)dst & 127) || (res && ((ld_res & 31) || ((uintptr_t)res & 127)))))
+        LWG_FAIL(LWG_ERR_UNSUPPORTED, "norm_apply: split-bf16 buffers need 32-channel granularity and 128-byte alignment (C=%d)", C);
+    if (lanes == 8 && !split) LWG_FAIL(LWG_ERR_UNSUPPORTED, "norm_apply: eight channels per thread is the split-bf16 kernel");
+    if ((long)N * H * W * (C >> 2) > (1l << 31) - 256) LWG_FAIL(LWG_ERR_UNSUPPORTED, "norm_apply: tensor too large for one launch");
+    ApplyArgs a = {};
+    a.raw = raw; a.C = C; a.N = N; a.H = H; a.W = W;
+    a.scale_shift = reinterpret_cast<const float2 *>(scale_shift);
+    a.relu = relu;
+    a.dst = dst; a.ld_dst = ld_dst;
+    a.res = res; a.ld_res = res ? ld_res : 0;
+    a.split = split;
+    a.nwarp = nwarp;
+    for (int k = 0; k < nwarp; ++k) { a.warp_src[k] = wsrc[k]; a.warp_n[k] = wn[k]; a.warp_T[k] = wT[k]; }
+    a.align_corners = align_corners;
+    return launch_apply(a, reinterpret_cast<hipStream_t>(stream), lanes);
+}
+
 int lwg_heads_backward_weight(const float *x, const float *dy8, int N, int H, int W, float *dw, void *ws, size_t ws_bytes,
                               lwg_stream_t stream)
 {

@@ -155,6 +155,87 @@ def stem_forward(x, w, precision="bf16x3", with_partials=True, max_workgroups=0)
     return y, partials
 
 
+def conv_variant_name(variant):
+    """Kernel family name of a variant number (lwg_generator_profile_variant_name)."""
+    return _lib.load().lwg_generator_profile_variant_name(int(variant)).decode()
+
+
+@torch.no_grad()
+def norm_conv_forward(x, w, stride=1, pad=0, transposed=False, precision="bf16x3", bn=0, in_scale_shift=None, raw_from=0):
+    """One layer of the inference path with its statistics epilogue (lwg_norm_conv_forward): x (N,H,W,Cin) fp32, w in PyTorch
+    layout -> (y raw (N,Ho,Wo,Cout), partials (nphase, N*Hm*Wm/128, Cout, 2) = per-tile (mean, M2), variant number).  bn 0: the
+    generator's tile-width rule.  in_scale_shift (N, Cin - raw_from, 2): channels >= raw_from of x are raw and normalised by the
+    kernel.  Outputs and workspace start as NaN, so an unwritten element shows."""
+    _chk(x, w, in_scale_shift)
+    cin, cout = (w.shape[0], w.shape[1]) if transposed else (w.shape[1], w.shape[0])
+    n, h, wd, _ = x.shape
+    d = _desc(x.shape, cin, cout, w.shape[2], stride, pad, transposed, precision)
+    ho, wo = _out_hw(h, wd, w.shape[2], stride, pad, transposed)
+    hm, wm, nphase = (h, wd, 4) if transposed else (ho, wo, 1)
+    if in_scale_shift is not None and tuple(in_scale_shift.shape) != (n, cin - raw_from, 2):
+        raise RuntimeError("norm_conv_forward: in_scale_shift (N, Cin - raw_from, 2) expected")
+    lib = _lib.load()
+    nb = lib.lwg_norm_conv_workspace_bytes(ctypes.byref(d))
+    if not nb:
+        raise _lib.LwgError(-2, lib.lwg_last_error().decode(errors="replace"))
+    nan = float("nan")
+    ws = torch.full((nb // 4 + 4,), nan, device=x.device, dtype=torch.float32)
+    y = torch.full((n, ho, wo, cout), nan, device=x.device, dtype=torch.float32)
+    partials = torch.full((nphase, max(n * hm * wm // 128, 1), cout, 2), nan, device=x.device, dtype=torch.float32)
+    variant = ctypes.c_int(-1)
+    _lib.check(lib.lwg_norm_conv_forward(ctypes.byref(d), _lib.ptr(x), _lib.ptr(w), int(bn), _lib.ptr(in_scale_shift), int(raw_from),
+                                         _lib.ptr(y), _lib.ptr(partials), ctypes.byref(variant), _lib.ptr(ws), nb, _lib.stream_ptr()))
+    return y, partials, variant.value
+
+
+@torch.no_grad()
+def norm_finalize(partials, n, gamma, beta, eps=1e-5):
+    """partials (nphase, mtiles, C, 2) -> scale_shift (N, C, 2) of InstanceNorm2d(affine, eps, biased variance) (lwg_norm_finalize)."""
+    _chk(partials, gamma, beta)
+    nphase, mtiles, c, two = partials.shape
+    if two != 2 or gamma.numel() != c or beta.numel() != c:
+        raise RuntimeError("norm_finalize: partials (nphase, mtiles, C, 2), gamma and beta (C,) expected")
+    ss = torch.full((n, c, 2), float("nan"), device=partials.device, dtype=torch.float32)
+    _lib.check(_lib.load().lwg_norm_finalize(_lib.ptr(partials), nphase, mtiles, int(n), c, _lib.ptr(gamma), _lib.ptr(beta), float(eps),
+                                             _lib.ptr(ss), _lib.stream_ptr()))
+    return ss
+
+
+def _slice_ptr(buf, channel_offset):
+    return ctypes.c_void_p(buf.data_ptr() + 4 * int(channel_offset))
+
+
+@torch.no_grad()
+def norm_apply(raw, scale_shift, relu=True, dst=None, dst_offset=0, res=None, res_offset=0, split=False, warps=(),
+               align_corners=False, lanes=0):
+    """The apply pass on its own (lwg_norm_apply): raw (N,H,W,C), scale_shift (N,C,2) -> dst = [relu](raw*scale + shift) [+ res]
+    [+ warps].  dst: an (N,H,W,ld_dst) fp32 buffer written at channel offset dst_offset (None: a fresh NaN-filled (N,H,W,C) one);
+    res likewise.  split: dst / res hold the split-bf16 format (per 32 channels [32 bf16 hi | 32 bf16 lo] in the same bytes).
+    warps: up to two (src (1 or N,H,W,C), flow (N,H,W,2)).  lanes 4 / 8 picks apply_kernel / apply8_kernel.  Returns dst."""
+    _chk(raw, scale_shift, dst, res, *[t for wp in warps for t in wp])
+    n, h, w, c = raw.shape
+    if tuple(scale_shift.shape) != (n, c, 2):
+        raise RuntimeError("norm_apply: scale_shift (N,C,2) expected")
+    if dst is None:
+        dst = torch.full((n, h, w, c), float("nan"), device=raw.device, dtype=torch.float32)
+    for t, off in ((dst, dst_offset), (res, res_offset)):
+        if t is not None and (tuple(t.shape[:3]) != (n, h, w) or off < 0 or off + c > t.shape[3]):
+            raise RuntimeError("norm_apply: dst / res are (N,H,W,ld) buffers holding channels offset .. offset + C")
+    if len(warps) > 2:
+        raise RuntimeError("norm_apply: at most two warp terms")
+    wa = []
+    for src, flow in warps:
+        if src.shape[0] not in (1, n) or tuple(src.shape[1:]) != (h, w, c) or tuple(flow.shape) != (n, h, w, 2):
+            raise RuntimeError("norm_apply: warp terms are (src (1 or N,H,W,C), flow (N,H,W,2))")
+        wa += [_lib.ptr(src), int(src.shape[0]), _lib.ptr(flow)]
+    wa += [None, 1, None] * (2 - len(warps))
+    _lib.check(_lib.load().lwg_norm_apply(_lib.ptr(raw), n, h, w, c, _lib.ptr(scale_shift), int(relu), _slice_ptr(dst, dst_offset),
+                                          int(dst.shape[3]), None if res is None else _slice_ptr(res, res_offset),
+                                          0 if res is None else int(res.shape[3]), int(split), len(warps), *wa, int(align_corners),
+                                          int(lanes), _lib.stream_ptr()))
+    return dst
+
+
 @torch.no_grad()
 def heads_backward_weight(x, dy8, out=None):
     """x (N,H,W,64), dy8 (N,H,W,8) (gradient wrt the pre-activation head outputs, channels 4-7 zero) -> dw (8,64,7,7)."""

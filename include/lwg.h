@@ -508,6 +508,63 @@ LWG_API int lwg_heads_inference(const float *x, int N, int H, int W, const float
                                 int precision, const float *bg, int bg_bs, float *color, float *mask, float *pred, int bands,
                                 void *workspace, size_t workspace_bytes, lwg_stream_t stream);
 
+/* Diagnostic entries (as lwg_stem_forward: for tests, not a hot path): the inference path's norm chain, link by link.  Every layer
+ * of lwg_generator_inference is conv -> per-tile (mean, M2) written by the conv's epilogue -> finalize -> apply (or, where the
+ * consumer is a halo kernel, the apply folded into that consumer's operand load).  Each link runs here on caller-supplied tensors
+ * through the launch code the generator runs.  Every argument is checked before the first HIP call.
+ *
+ * lwg_norm_conv_forward: one layer as the generator launches it -- the non-general kernels with their statistics epilogue.
+ *   d: precision 0 (exact fp32) or 1 (bf16x3), transposed 0 or 1; x (N,H,W,Cin) plain fp32 NHWC; w in PyTorch layout (as
+ *     lwg_conv2d_forward); the entry re-lays the weights out, splits x (precision 1) and keeps the zero run behind it.
+ *   The output grid per image (Hm x Wm: Ho x Wo, or H x W for a transposed conv, whose four output parities are four PHASES
+ *     p = 2*py + px holding the pixels (2i+py, 2j+px)) must be a multiple of 128 pixels.
+ *   bn: output channels per workgroup tile, 32 / 64 / 128 passed to the dispatcher as given; 0 = the generator's rule: 128 once
+ *     Cout % 128 == 0 and the launch has >= 256 such tiles, else 64 (exact fp32 with few tiles: 32).  A transposed layer runs
+ *     unfused on the 128-channel tile when precision 1 and Cout % 128 == 0, else as one workgroup walking all four phases of a
+ *     64-channel tile, whatever bn says.  What the dispatcher refuses is returned with its code.
+ *   y (N,Ho,Wo,Cout) raw output; partials (nphase, mtiles, Cout, 2), mtiles = N*Hm*Wm/128: (mean, M2 = sum of squared deviations
+ *     from that mean) of y over 128 output pixels of one phase and channel.  WHICH 128 pixels partial t of phase p covers:
+ *       - ring and fp32 kernels (conv_igemm_bf16x3, conv_igemm_dma_f32, conv_igemm_f32): pixels 128t .. 128t+127 of the phase's
+ *         grid flattened as (image, hm, wm), images in order -- a run of 128 consecutive pixels; the 256-row ring tile writes
+ *         the two runs 2u, 2u+1 of its workgroup u;
+ *       - halo kernels (conv3x3_halo_bf16x3, plain and transposed): the 4-row x 32-column blocks of the Hm x Wm grid, numbered
+ *         row-major within the image, images in order: t = image * (Hm/4)*(Wm/32) + (hm/4) * (Wm/32) + wm/32.  The tall (8 x 32)
+ *         tile writes two of them: its upper block at that index and its lower block Wm/32 entries (one block row) further.
+ *       At Wm == 32 the two numberings coincide.  Within a partial the 128 values are reduced as four groups of 32 (mean and M2
+ *       each) combined by Chan's formula; the order inside a group is the kernel's own.
+ *   variant_host (optional, HOST int): the kernel family that ran, an index for lwg_generator_profile_variant_name.
+ *   in_scale_shift (optional, precision 1): (N, Cin - raw_from, 2) -- channels >= raw_from of x are then a producer's RAW output
+ *     which the kernel normalises itself, relu(x * scale + shift) and the hi/lo split, zero padding applied AFTER it; raw_from a
+ *     multiple of 32.  Only the halo kernels take it: LWG_ERR_UNSUPPORTED elsewhere.
+ *   workspace: lwg_norm_conv_workspace_bytes, 16-byte aligned, scratch only.  Enqueued on the stream, no synchronisation.
+ *
+ * lwg_norm_finalize: partials (nphase, mtiles, C, 2) as above, mtiles = N * tiles per image -> scale_shift (N, C, 2) =
+ *   (gamma * inv, beta - mean * gamma * inv), inv = 1 / sqrt(var + eps), var the BIASED variance of the image's nphase * mtiles/N
+ *   * 128 samples: Chan's combination of the partials in double, rounded to fp32 once per output.
+ *   Conditioning contract: the between-tile term is computed as sum(mean_t^2) - cnt * mean^2, which cancels when |mean| >> std.
+ *   For |mean| / std <= 2^12 both outputs are within 2 fp32 ulp of the exactly combined value (CPU emulations of the kernel's
+ *   arithmetic put the worst at 0.5 to 0.7 ulp); beyond, the error grows with the square of the ratio (1 to 6 ulp at 2^14, 12 to
+ *   90 at 2^16, depending on the partials) -- there the fp32 rounding of shift itself, ~ratio * 2^-24 of a normalised unit, already
+ *   exceeds what apply can deliver.  tests/test_gpu_norm_chain.py asserts the contract and prints the figures beyond it.
+ *
+ * lwg_norm_apply: dst = [relu](raw * scale + shift) [+ res] [+ sum_k grid_sample(warp_src_k, warp_T_k)] per pixel and channel.
+ *   raw (N,H,W,C) dense fp32; scale_shift (N,C,2); dst: pixel stride ld_dst >= C floats (a channel slice of a wider buffer, offset
+ *     already applied); res likewise with ld_res, or NULL; split 1: dst is written, and res read, in the split-bf16 format (per 32
+ *     channels [32 bf16 hi | 32 bf16 lo]; C, strides % 32 == 0, 128-byte aligned), split 0: both fp32;
+ *   nwarp 0..2 Liquid-Warping terms: warp_src_k (warp_n_k,H,W,C) fp32 with warp_n_k in {1 (shared), N}, warp_T_k (N,H,W,2) the
+ *     flow, bilinear with zero padding as lwg_grid_sample_nhwc, added AFTER the activation in the order k = 0, 1;
+ *   lanes: 0 = the launcher's choice, 4 = apply_kernel (four channels per thread), 8 = apply8_kernel (split only).  C % 4 == 0. */
+LWG_API size_t lwg_norm_conv_workspace_bytes(const lwg_conv2d_desc *d);
+LWG_API int lwg_norm_conv_forward(const lwg_conv2d_desc *d, const float *x, const float *w, int bn, const float *in_scale_shift,
+                                  int raw_from, float *y, float *partials, int *variant_host, void *workspace,
+                                  size_t workspace_bytes, lwg_stream_t stream);
+LWG_API int lwg_norm_finalize(const float *partials, int nphase, int mtiles, int N, int C, const float *gamma, const float *beta,
+                              float eps, float *scale_shift, lwg_stream_t stream);
+LWG_API int lwg_norm_apply(const float *raw, int N, int H, int W, int C, const float *scale_shift, int relu, float *dst, int ld_dst,
+                           const float *res, int ld_res, int split, int nwarp, const float *warp_src0, int warp_n0,
+                           const float *warp_T0, const float *warp_src1, int warp_n1, const float *warp_T1, int align_corners,
+                           int lanes, lwg_stream_t stream);
+
 /* Generator-side adversarial term (models/impersonator_trainer.py:369-371): loss = mean((D(x) - target)^2) on
  * x (bs,input_nc,is,is) NCHW and its gradient wrt x (same shape); the discriminator's parameters get no gradient. */
 LWG_API int lwg_discriminator_input_grad(lwg_discriminator *d, const float *x_nchw, int bs, float target, float *loss_device,

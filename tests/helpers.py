@@ -971,3 +971,562 @@ def resize_flow_float64(T, h, w):
     """F.interpolate(bilinear, align_corners=True) of a flow (bs, H, W, 2) to (bs, h, w, 2), float64"""
     import torch.nn.functional as F
     return F.interpolate(T.double().permute(0, 3, 1, 2), size=(h, w), mode="bilinear", align_corners=True).permute(0, 2, 3, 1).contiguous()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The inference path's norm chain link by link (lwg_norm_conv_forward, lwg_norm_finalize, lwg_norm_apply; include/lwg.h states
+# which 128 pixels a partial covers and the conditioning contract of finalize).  tests/test_norm_chain_cases.py proves on the
+# CPU the conditions the exact expectations rest on and that the listed mutants miss them; tests/test_gpu_norm_chain.py holds
+# the kernels to them.
+IN_EPS = float(np.float32(1e-5))   # kInEps widened to double, as in_finalize_kernel widens it
+
+# name -> (Cin, Cout, k, stride, pad, transposed, H, W, N(ncu), precision, bn, partition, kernel name the profiler must show)
+_HALO_K, _RING_K, _DMA_K, _F32_K = "conv3x3_halo_bf16x3", "conv_igemm_bf16x3", "conv_igemm_dma_f32", "conv_igemm_f32"
+NORM_STAT_CASES = {
+    "halo64": (32, 64, 3, 1, 1, False, 4, 32, lambda ncu: 1, "bf16x3", 64, "blocks", _HALO_K + "<64,1,2,3,32,128,0,false>"),
+    # two block columns, six blocks per image, blocks that are no runs of consecutive pixels
+    "halo64_8x64": (32, 64, 3, 1, 1, False, 8, 64, lambda ncu: 3, "bf16x3", 64, "blocks", _HALO_K + "<64,1,2,3,32,128,0,false>"),
+    "halo128": (32, 128, 3, 1, 1, False, 12, 32, lambda ncu: -(-ncu // 3), "bf16x3", 128, "blocks", _HALO_K + "<128,2,2,4,32,128,0,false>"),
+    "halo_tall": (32, 128, 3, 1, 1, False, 8, 32, lambda ncu: ncu, "bf16x3", 128, "blocks", _HALO_K + "<128,2,2,4,32,256,0,false>"),
+    "ct_narrow": (32, 64, 3, 2, 1, True, 4, 32, lambda ncu: 1, "bf16x3", 0, "blocks", _HALO_K + "<64,1,2,3,32,128,1,false>"),
+    "ct_wide": (32, 128, 3, 2, 1, True, 16, 32, lambda ncu: -(-ncu // 4), "bf16x3", 0, "blocks", _HALO_K + "<128,2,2,4,32,128,1,false>"),
+    "ring64": (32, 64, 1, 1, 0, False, 4, 32, lambda ncu: 1, "bf16x3", 64, "runs", _RING_K + "<64,1,2,3,0,128>"),
+    "ring128": (32, 512, 3, 2, 1, False, 24, 64, lambda ncu: 44, "bf16x3", 128, "runs", _RING_K + "<128,2,2,4,0,128>"),
+    "ring_tall": (32, 128, 1, 1, 0, False, 8, 32, lambda ncu: ncu, "bf16x3", 128, "runs", _RING_K + "<128,2,2,3,0,256>"),
+    # a map wider than 128 on the ring: a run is part of one row (the TC2 > 0 epilogue of igemm_epilogue is instantiated by no kernel)
+    "ring_wide_map": (32, 64, 1, 1, 0, False, 4, 192, lambda ncu: 2, "bf16x3", 64, "runs", _RING_K + "<64,1,2,3,0,128>"),
+    # exact fp32, non-general kernels
+    "dma32": (32, 64, 3, 1, 1, False, 8, 16, lambda ncu: 1, "fp32", 32, "runs", _DMA_K + "<32,1,1,0,3>"),
+    "dma64": (32, 64, 3, 1, 1, False, 8, 16, lambda ncu: 1, "fp32", 64, "runs", _DMA_K + "<64,1,2,0,3>"),
+    "dma128": (32, 128, 3, 1, 1, False, 8, 16, lambda ncu: 1, "fp32", 128, "runs", _DMA_K + "<128,2,2,0,3>"),
+    "reg128": (32, 128, 1, 1, 0, False, 4, 32, lambda ncu: ncu + 1, "fp32", 128, "runs", _F32_K + "<128,2,2,false,0,false,false>"),
+    "small_cin": (8, 64, 7, 1, 3, False, 16, 16, lambda ncu: 1, "fp32", 64, "runs", _F32_K + "<64,1,2,true,0,false,false>"),
+    "ct_fused_f32": (32, 64, 3, 2, 1, True, 4, 32, lambda ncu: 1, "fp32", 0, "runs", _DMA_K + "<64,1,2,0,3>"),
+}
+NORM_F32_CASES = ("dma32", "dma64", "dma128", "reg128", "small_cin", "ct_fused_f32")
+
+
+def norm_case(name, ncu=EXACT_NCU):
+    """ConvCase of a NORM_STAT_CASES row with its batch fixed, plus .bn, .partition, .kernel, .name"""
+    cin, cout, k, stride, pad, transposed, H, W, n_of, precision, bn, partition, kernel = NORM_STAT_CASES[name]
+    c = ConvCase("fwd", cin, cout, k, stride, pad, H, W, n_of(ncu), transposed=transposed, precision=precision)
+    c.bn, c.partition, c.kernel, c.name = bn, partition, kernel, name
+    return c
+
+
+def norm_grid(case):
+    """(nphase, Hm, Wm): the phase grid per image whose pixels the partials tile"""
+    return (4, case.H, case.W) if case.transposed else (1,) + case.out_hw()
+
+
+def _ct_taps(co):
+    """transposed conv: the (ky, kx) of output channel co's tap per output parity class p = 2 py + px.  Row 2i + py is fed by
+    ky = 1 (py 0: input row i) or by ky in {2 (input row i), 0 (input row i + 1)} (py 1); columns alike."""
+    odd_y, odd_x = ((2, 0)[co & 1], (2, 0)[(co >> 1) & 1]) if co >= 2 else (2, 2)   # channels 0, 1 never read past the border
+    return [(1, 1), (1, odd_x), (odd_y, 1), (odd_y, odd_x)]
+
+
+def onehot_stat_operands(case, seed=0):
+    """The exact statistics family.  x (N,H,W,Cin) NHWC: integers in [-2, 2], every input channel with its own distribution --
+    channel 0 all zero, 1 constant per image, 2 only +-2, 3 rows alternating {1, 2} / {-2, -1} (group means far apart), the others
+    uniform on a subset of {-2..2} that depends on the channel; images differ.  w (PyTorch layout) one-hot: output channel co takes
+    input channel co % Cin at a tap that varies with co (the centre for channels 0 and 1, which thus stay all-zero / constant --
+    per phase for a transposed conv),
+    value 2^e(co), e in [-6, 6]; a transposed conv gets one tap per output parity class (_ct_taps), the sign alternating with the
+    class.  -> (x, w, ci (Cout), e (Cout))."""
+    g = torch.Generator().manual_seed(7000 + seed)
+    N, H, W, cin, cout, k = case.N, case.H, case.W, case.cin, case.cout, case.k
+    x = torch.zeros(N, H, W, cin)
+    for c in range(cin):
+        if c == 0:
+            continue
+        if c == 1:
+            x[..., c] = torch.tensor([2.0, -1.0, 1.0, -2.0])[torch.arange(N) % 4].view(N, 1, 1)
+        elif c == 2:
+            x[..., c] = torch.randint(0, 2, (N, H, W), generator=g).float() * 4 - 2
+        elif c == 3:
+            v = torch.randint(1, 3, (N, H, W), generator=g).float()
+            x[..., c] = torch.where((torch.arange(H) % 2 == 0).view(1, H, 1), v, -v)
+        else:
+            lo, hi = -2 + (c % 3), 2 - ((c // 3) % 2)
+            x[..., c] = torch.randint(lo, hi + 1, (N, H, W), generator=g).float()
+    co = torch.arange(cout)
+    ci = co % cin
+    e = (co * 7) % 13 - 6
+    w = torch.zeros(case.w_shape())
+    for o in range(cout):
+        s = 2.0 ** int(e[o])
+        if case.transposed:
+            for p, (ky, kx) in enumerate(_ct_taps(o)):
+                w[ci[o], o, ky, kx] = s if p in (0, 3) else -s
+        else:
+            tap = (k * k) // 2 if o < 2 else (o // cin + o) % (k * k)
+            w[o, ci[o], tap // k, tap % k] = s
+    return x, w, ci, e
+
+
+def onehot_conv_reference(case, x, w):
+    """The raw output (N,Ho,Wo,Cout) float64 of a one-hot weight tensor as shifted, scaled copies of x's channels: no conv."""
+    N, H, W, cin, cout, k = case.N, case.H, case.W, case.cin, case.cout, case.k
+    Ho, Wo = case.out_hw()
+    y = torch.zeros(N, Ho, Wo, cout, dtype=torch.float64)
+    xd = x.double()
+    if case.transposed:
+        xp = torch.nn.functional.pad(xd, (0, 0, 0, 1, 0, 1))   # one zero row / column behind the image
+        wt = w.permute(1, 0, 2, 3)                              # (Cout, Cin, 3, 3)
+        for ky in range(3):
+            for kx in range(3):
+                nz = wt[:, :, ky, kx].abs().sum(1).nonzero().flatten()
+                if not len(nz):
+                    continue
+                ci = wt[nz, :, ky, kx].abs().argmax(1)
+                val = wt[nz, ci, ky, kx].double()
+                py, dy = (0, 0) if ky == 1 else (1, 1 if ky == 0 else 0)
+                px, dx = (0, 0) if kx == 1 else (1, 1 if kx == 0 else 0)
+                y[:, py::2, px::2, nz] = xp[:, dy:dy + H, dx:dx + W][..., ci] * val
+        return y
+    p, s = case.pad, case.stride
+    xp = torch.nn.functional.pad(xd, (0, 0, p, p, p, p))
+    for kh in range(k):
+        for kw in range(k):
+            nz = w[:, :, kh, kw].abs().sum(1).nonzero().flatten()
+            if not len(nz):
+                continue
+            ci = w[nz, :, kh, kw].abs().argmax(1)
+            y[..., nz] = xp[:, kh:kh + s * (Ho - 1) + 1:s, kw:kw + s * (Wo - 1) + 1:s][..., ci] * w[nz, ci, kh, kw].double()
+    return y
+
+
+def conv_reference_nhwc(case, x, w):
+    """float64 F.conv2d / F.conv_transpose2d of NHWC x -> NHWC y"""
+    return case.op(x.permute(0, 3, 1, 2), w).permute(0, 2, 3, 1).contiguous()
+
+
+def phase_views(case, y):
+    """raw output (N,Ho,Wo,C) -> (nphase, N, Hm, Wm, C): the phase grids (phase p = 2 py + px of a transposed conv holds the
+    output pixels (2i + py, 2j + px))"""
+    if not case.transposed:
+        return y.unsqueeze(0)
+    return torch.stack([y[:, py::2, px::2] for py in (0, 1) for px in (0, 1)])
+
+
+STAT_MUTANTS = ("other_partition", "swap_phases", "image0_tiles", "channel32", "channel64", "tall_stride")
+
+
+def stat_partition(partition, N, Hm, Wm):
+    """(mtiles, 128) flat pixel indices into (N, Hm, Wm) of every partial, as include/lwg.h documents them: 'runs' = 128 consecutive
+    pixels, images in order; 'blocks' = 4 x 32 blocks numbered row-major within the image."""
+    idx = torch.arange(N * Hm * Wm)
+    if partition == "runs":
+        return idx.view(-1, 128)
+    assert partition == "blocks" and Hm % 4 == 0 and Wm % 32 == 0
+    return idx.view(N, Hm // 4, 4, Wm // 32, 32).permute(0, 1, 3, 2, 4).reshape(-1, 128)
+
+
+def stat_expected(case, y, mutant=None):
+    """float64 (mean, M2), each (nphase, mtiles, C), of the raw output y (N,Ho,Wo,C) under the documented partition.  mutant:
+      'other_partition'  runs where blocks are documented and the reverse;
+      'swap_phases'      phases 1 and 2 exchanged;
+      'image0_tiles'     image n reads image 0's pixels;
+      'channel32' / 'channel64'  channel c holds channel (c + 32 / 64) % C;
+      'tall_stride'      an 8 x 32 tile writes its lower block one block row too far (NaN where nothing lands)."""
+    assert mutant is None or mutant in STAT_MUTANTS
+    nphase, Hm, Wm = norm_grid(case)
+    N, C = y.shape[0], y.shape[-1]
+    part = case.partition
+    if mutant == "other_partition":
+        part = "runs" if part == "blocks" else "blocks"
+    idx = stat_partition(part, N, Hm, Wm)
+    if mutant == "image0_tiles":
+        idx = idx % (Hm * Wm)
+    v = phase_views(case, y.double()).reshape(nphase, N * Hm * Wm, C)[:, idx]   # (nphase, mtiles, 128, C)
+    mean = v.mean(2)
+    m2 = ((v - mean[:, :, None]) ** 2).sum(2)
+    if mutant == "swap_phases":
+        assert nphase == 4
+        mean, m2 = mean[[0, 2, 1, 3]], m2[[0, 2, 1, 3]]
+    if mutant in ("channel32", "channel64"):
+        sh = (torch.arange(C) + int(mutant[7:])) % C
+        mean, m2 = mean[..., sh], m2[..., sh]
+    if mutant == "tall_stride":
+        bx, by = Wm // 32, Hm // 4
+        assert part == "blocks" and by % 2 == 0
+        out = []
+        for t in (mean, m2):
+            t = t.view(nphase, N, by, bx, C)
+            moved = torch.full_like(t, float("nan"))
+            moved[:, :, 0::2] = t[:, :, 0::2]
+            moved[:, :, 2::2] = t[:, :, 1:-1:2]          # lower blocks land on the next tile's upper block
+            out.append(moved.view(nphase, -1, C))
+        mean, m2 = out
+    return mean, m2
+
+
+def two_level_stats_f32(v, rng=None):
+    """The epilogues' reduction restated in numpy float32, v (..., 128) float32 -> (mean, M2) float32: four groups of 32 -- sum,
+    division by 32, squared deviations from the group mean -- combined by Chan's formula with the factor 32, every operation a
+    separately rounded fp32 one, each sum SEQUENTIAL (the worst order a kernel could choose).  rng: shuffle the 128 values first."""
+    v = np.asarray(v, dtype=np.float32)
+    if rng is not None:
+        v = np.take_along_axis(v, np.argsort(rng.random(v.shape), axis=-1), axis=-1)
+    gsh = v.reshape(v.shape[:-1] + (4, 32))
+    s = np.zeros(gsh.shape[:-1], dtype=np.float32)
+    for i in range(32):
+        s = s + gsh[..., i]
+    mu = s * np.float32(1.0 / 32.0)
+    q = np.zeros_like(s)
+    for i in range(32):
+        d = gsh[..., i] - mu
+        q = q + d * d
+    mean = np.zeros(s.shape[:-1], dtype=np.float32)
+    for w in range(4):
+        mean = mean + mu[..., w]
+    mean = mean * np.float32(0.25)
+    m2 = np.zeros_like(mean)
+    for w in range(4):
+        d = mu[..., w] - mean
+        m2 = m2 + (q[..., w] + np.float32(32.0) * d * d)
+    return mean, m2
+
+
+# Random statistics: the restatement above against float64 on the same fp32 values, over norm_random_tiles() -- per family the
+# worst |mean - ref| / max |y| and |M2 - ref| / max ref M2 (the convention of STEM_M2_REL), measured by tests/test_norm_chain_cases.py,
+# which prints them and asserts that none exceeds the figures below.  The GPU assertions use 4 x them (NORM_STAT_REL); the raw
+# output of Gaussian operands is held to the 'offset' figures (its tile means wander by a few sigma / sqrt(128) at most).
+# family -> (mean figure, M2 figure) as measured (8.29e-9 / 1.74e-7, 4.49e-8 / 1.43e-7, 1.31e-7 / 4.67e-5).  At |mean| / std = 2^10 the
+# fp32 group means carry an error of ~2^-14 std, which the between-group term of Chan's formula turns into ~5e-5 of M2.
+NORM_STAT_MEASURED = {"gauss": (9e-9, 1.8e-7), "offset": (4.6e-8, 1.8e-7), "ratio1024": (1.4e-7, 4.8e-5)}
+NORM_STAT_REL = {k: (4 * v[0], 4 * v[1]) for k, v in NORM_STAT_MEASURED.items()}
+NORM_RANDOM_FAMILIES = ("gauss", "offset", "ratio1024")
+
+
+def norm_random_tiles(family, tiles=256, C=16, seed=0):
+    """(tiles, C, 128) float32 samples of a raw output: 'gauss' N(0, s_c^2); 'offset' mean of a few sigma per channel;
+    'ratio1024' |mean| / std = 2^10 in every channel."""
+    g = torch.Generator().manual_seed(8000 + seed + NORM_RANDOM_FAMILIES.index(family))
+    z = torch.randn(tiles, C, 128, generator=g, dtype=torch.float64)
+    s = torch.pow(2.0, torch.randint(-4, 5, (1, C, 1), generator=g).double())
+    m = {"gauss": 0.0, "offset": torch.randn(1, C, 1, generator=g, dtype=torch.float64) * 3, "ratio1024": 1024.0}[family]
+    return ((z + m) * s).float()
+
+
+def stat_errors(mean, m2, ref_mean, ref_m2, ymax):
+    """(mean error / max |y|, M2 error / max ref M2): the two figures NORM_STAT_REL bounds"""
+    return (float((torch.as_tensor(mean).double() - ref_mean).abs().max()) / ymax,
+            float((torch.as_tensor(m2).double() - ref_m2).abs().max()) / float(ref_m2.max()))
+
+
+# ---- finalize
+def finalize_reference(mean, m2, N, gamma, beta, exact=False):
+    """scale_shift (N, C, 2) float64 BEFORE the final rounding, from partials (nphase, mtiles, C) given as float64 (the fp32
+    partials widened): Chan's combination, biased variance over the image's nphase * tiles * 128 samples, eps = IN_EPS.
+    exact: the combination in exact rationals (fractions) -- for ill-conditioned synthetic partials; otherwise float64 in the
+    cancellation-free form sum M2 + 128 sum (mean_t - mean)^2."""
+    nphase, mtiles, C = mean.shape
+    tiles = mtiles // N
+    mu = mean.view(nphase, N, tiles, C).permute(1, 3, 0, 2).reshape(N, C, -1).double()
+    q = m2.view(nphase, N, tiles, C).permute(1, 3, 0, 2).reshape(N, C, -1).double()
+    cnt = mu.shape[-1]
+    if exact:
+        from fractions import Fraction
+        gm = torch.zeros(N, C, dtype=torch.float64)
+        var = torch.zeros(N, C, dtype=torch.float64)
+        for n in range(N):
+            for c in range(C):
+                ms = [Fraction(v) for v in mu[n, c].tolist()]
+                qs = [Fraction(v) for v in q[n, c].tolist()]
+                m = sum(ms) / cnt
+                gm[n, c] = float(m)
+                var[n, c] = float((sum(qs) + 128 * sum((a - m) ** 2 for a in ms)) / (cnt * 128))
+    else:
+        gm = mu.mean(-1)
+        var = (q.sum(-1) + 128 * ((mu - gm[..., None]) ** 2).sum(-1)) / (cnt * 128)
+    inv = 1.0 / torch.sqrt(var + IN_EPS)
+    ga, be = gamma.double().view(1, C), beta.double().view(1, C)
+    return torch.stack([ga * inv, be - gm * ga * inv], dim=-1)
+
+
+def finalize_emulated(mean, m2, N, gamma, beta):
+    """in_finalize_kernel's double arithmetic restated in numpy: 16 slices walk the tiles t = slice, slice + 16, ... of each phase
+    in turn, the slices are added in order, between = sum mean^2 - cnt mean^2 (clamped at 0) -> (N, C, 2) float32."""
+    nphase, mtiles, C = mean.shape
+    tiles = mtiles // N
+    mu = mean.view(nphase, N, tiles, C).double().numpy()
+    q = m2.view(nphase, N, tiles, C).double().numpy()
+    sm, sq, s2 = (np.zeros((16, N, C)) for _ in range(3))
+    for p in range(nphase):
+        for t in range(tiles):
+            sm[t % 16] += mu[p, :, t]
+            sq[t % 16] += mu[p, :, t] * mu[p, :, t]
+            s2[t % 16] += q[p, :, t]
+    tot = [np.zeros((N, C)) for _ in range(3)]
+    for k in range(16):
+        tot[0] = tot[0] + sm[k]
+        tot[1] = tot[1] + sq[k]
+        tot[2] = tot[2] + s2[k]
+    cnt = float(nphase * tiles)
+    m = tot[0] / cnt
+    between = np.maximum(tot[1] - cnt * m * m, 0.0)
+    var = (tot[2] + 128.0 * between) / (cnt * 128.0)
+    inv = 1.0 / np.sqrt(var + IN_EPS)
+    ga, be = gamma.double().numpy()[None], beta.double().numpy()[None]
+    return torch.from_numpy(np.stack([(ga * inv).astype(np.float32), (be - m * ga * inv).astype(np.float32)], axis=-1))
+
+
+def ulp_error(got, ref64):
+    """|got - ref| in units of the fp32 spacing at the reference, elementwise (float64 tensor)"""
+    ref32 = ref64.float()
+    ulp = torch.from_numpy(np.spacing(np.abs(ref32.numpy()).astype(np.float32))).double()
+    return (got.double() - ref64).abs() / ulp
+
+
+def synthetic_partials(nphase, tiles, N, C, ratio=None, seed=0):
+    """fp32 partials (nphase, N * tiles, C) each of mean and M2, as tiles of N(m_c, s_c^2) samples would give them: the tile means
+    scatter by s / sqrt(128) around m, M2 ~ s^2 chi^2_127.  Channel 0 is constant (mean 3, M2 0), channel 1 all zero.  ratio:
+    |m_c| / s_c for every other channel (None: a few sigma either way).  gamma, beta seeded alike."""
+    g = torch.Generator().manual_seed(9000 + 131 * nphase + 17 * tiles + C + seed)
+    r = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)
+    s = torch.pow(2.0, torch.randint(-3, 4, (C,), generator=g).double())
+    m = (r(C) * 3 * s) if ratio is None else s * ratio * (torch.randint(0, 2, (C,), generator=g).double() * 2 - 1)
+    if ratio is None:
+        m = m + r(N, 1, C).expand(nphase, N, tiles, C).reshape(nphase, N * tiles, C) * s   # images differ
+    mean = m + r(nphase, N * tiles, C) * s / 128 ** 0.5
+    m2 = s * s * (127 + (2 * 127) ** 0.5 * r(nphase, N * tiles, C)).clamp(min=1.0)
+    mean[..., 0], m2[..., 0] = 3.0, 0.0
+    mean[..., 1], m2[..., 1] = 0.0, 0.0
+    gamma = (torch.rand(C, generator=g) + 0.5) * (torch.randint(0, 2, (C,), generator=g) * 2 - 1).float()
+    beta = torch.randn(C, generator=g) * 0.5
+    return mean.float(), m2.float(), gamma, beta
+
+
+# ---- apply
+APPLY_MUTANTS = ("no_relu", "res_lo_dropped", "ld_dst_is_c", "ld_res_is_c", "shared_per_sample", "per_sample_shared",
+                 "swap_hw", "other_align", "second_warp_ignored")
+# Random flows: the kernel computes the tap weights in fp32 (sample.h), the reference in float64.  The weights' fp32 error moves an
+# output by at most this fraction of S = |v s| + |t| + |res| + sum |w src| (float64 weights); measured over the random cases by
+# tests/test_norm_chain_cases.py from an fp32 restatement of sample.h (it prints the figure and asserts it stays below), never tuned
+# on the device.  The assertion allows 2^-19 S (21 fp32 operations of relative rounding 2^-24 each) plus 4 x this.
+APPLY_TAP_MEASURED = 3.6e-6   # 0 (no warp) to 3.55e-6 over the sixteen random cases: a coordinate near 2^5 carries 2^-19 of absolute error
+APPLY_REL = 2.0 ** -19 + 4 * APPLY_TAP_MEASURED
+
+
+class ApplyCase(object):
+    """One lwg_norm_apply call.  warps: tuple of 'shared' / 'per_sample' (0 to 2 entries); res: None, 'fp32' or 'split' (the
+    latter with a split destination only); every buffer is built by apply_operands."""
+
+    def __init__(self, family, N, H, W, C, relu, warps, align, res, seed):
+        self.family, self.N, self.H, self.W, self.C, self.relu, self.warps, self.align, self.res, self.seed = \
+            family, N, H, W, C, relu, tuple(warps), align, res, seed
+
+
+def apply_flow(N, H, W, g, random=False):
+    """(N,H,W,2) fp32 flow.  Exact family: multiples of 1/16 in [-2.5, 2.5] -- g + 1, its product with any size below 2^10, the
+    - 1 and the halving of sample.h::unnormalize are then exact in fp32 for EITHER align_corners and any H, W (the lattice cases of
+    sample_grid need power-of-two sizes), every weight a multiple of 2^-10 -- with the border coordinates -1, +1, the value -2 the
+    generator's flows carry (a patch and single pixels) and coordinates outside the image.  random: uniform on [-1.2, 1.2] with a
+    -2 patch, as helpers.train_batch."""
+    if random:
+        T = torch.rand(N, H, W, 2, generator=g) * 2.4 - 1.2
+    else:
+        T = torch.randint(-40, 41, (N, H, W, 2), generator=g).float() / 16
+        T[0, 0, :6, 0] = torch.tensor([-1.0, 1.0, -1.0, 1.0, -2.0, 2.5])
+        T[0, 0, :6, 1] = torch.tensor([-1.0, 1.0, 1.0, -1.0, 0.5, -2.5])
+    T[N - 1, H // 2:, W // 4:W // 2] = -2.0
+    return T
+
+
+@functools.lru_cache(maxsize=None)
+def apply_operands(case):
+    """dict of fp32 CPU tensors: raw (N,H,W,C), ss (N,C,2), res (N,H,W,C) or None, warps [(src (1 or N,H,W,C), flow (N,H,W,2))].
+    Exact family: raw = integers in [-8, 8] / 4; scale in {+-2^e, +-1.5 * 2^e}, e in [-2, 2]; shift = m / 16, |m| <= 64, both
+    signs; res = n / 256, |n| <= 511 (it needs its lo term); warp sources integers in [-8, 8]; flows from apply_flow.  Every
+    product and partial sum is a multiple of 2^-10 below 2^7: exact in fp32 in any order, contracted or not.  Shared: read-only."""
+    g = torch.Generator().manual_seed(11000 + case.seed)
+    N, H, W, C = case.N, case.H, case.W, case.C
+    rnd = case.family == "random"
+    if rnd:
+        raw = torch.randn(N, H, W, C, generator=g)
+        ss = torch.stack([torch.randn(N, C, generator=g), 0.5 * torch.randn(N, C, generator=g)], dim=-1).contiguous()
+        res = torch.randn(N, H, W, C, generator=g) if case.res else None
+        if case.res == "split":   # the operand IS the split buffer: what hi + lo carries
+            hi, lo = bf16_split_f32(res)
+            res = hi + lo
+    else:
+        raw = torch.randint(-8, 9, (N, H, W, C), generator=g).float() / 4
+        e = torch.randint(-2, 3, (N, C), generator=g).float()
+        mant = torch.where(torch.randint(0, 2, (N, C), generator=g) == 0, torch.tensor(1.0), torch.tensor(1.5))
+        sign = torch.randint(0, 2, (N, C), generator=g).float() * 2 - 1
+        ss = torch.stack([sign * mant * torch.pow(2.0, e), grid((N, C), g, 64, 16.0)], dim=-1).contiguous()
+        res = grid((N, H, W, C), g, 511, 256.0) if case.res else None
+    warps = []
+    for kind in case.warps:
+        xn = 1 if kind == "shared" else N
+        src = torch.randn(xn, H, W, C, generator=g) if rnd else torch.randint(-8, 9, (xn, H, W, C), generator=g).float()
+        warps.append((src, apply_flow(N, H, W, g, rnd)))
+    return dict(raw=raw, ss=ss, res=res, warps=warps)
+
+
+def apply_reference(case, ops=None, mutant=None, with_S=False):
+    """The apply pass in float64: [relu](raw * scale + shift) [+ res] [+ sum_k grid_sample(src_k, flow_k)] -> (N,H,W,C), the warps
+    from helpers.grid_sample_restated.  with_S: also S = |v s| + |t| + |res| + sum_k sum_taps |w src|.  mutant (APPLY_MUTANTS; the
+    ld_* ones are layout mutants, see apply_layout_mutant; swap_hw / other_align are grid_sample_restated's): the way a kernel goes wrong."""
+    o = ops or apply_operands(case)
+    N, H, W, C = case.N, case.H, case.W, case.C
+    v, s, t = o["raw"].double(), o["ss"][:, None, None, :, 0].double(), o["ss"][:, None, None, :, 1].double()
+    y = v * s + t
+    S = (v * s).abs() + t.abs()
+    if case.relu and mutant != "no_relu":
+        y = y.clamp(min=0)
+    if o["res"] is not None:
+        r = o["res"].double()
+        if mutant == "res_lo_dropped":
+            r = o["res"].bfloat16().double()
+        y = y + r
+        S = S + r.abs()
+    for k, (src, flow) in enumerate(o["warps"]):
+        if mutant == "second_warp_ignored" and k == 1:
+            continue
+        x = src
+        if mutant == "shared_per_sample" and src.shape[0] == 1 and N > 1:
+            x = torch.cat([src, torch.zeros(N - 1, H, W, C)])   # images 1.. read whatever lies behind the one source: not it
+        if mutant == "per_sample_shared" and src.shape[0] > 1:
+            x = src[:1]
+        xc = x.permute(0, 3, 1, 2)
+        align = bool(case.align) != (mutant == "other_align")
+        smut = "swap_hw" if mutant == "swap_hw" else None
+        y = y + grid_sample_restated(xc, flow, align, smut).permute(0, 2, 3, 1)
+        S = S + grid_sample_restated(src.permute(0, 3, 1, 2).abs(), flow, case.align).permute(0, 2, 3, 1)
+    return (y, S) if with_S else y
+
+
+def grid_taps_f32(flow, H, W, align):
+    """sample.h::grid_taps restated in numpy float32, operation by operation -> (x0, y0 int64, weights (…,4) float32 nw ne sw se)"""
+    f = np.float32
+    gx, gy = flow[..., 0].numpy().astype(f), flow[..., 1].numpy().astype(f)
+
+    def unn(gv, size):
+        if align:
+            return ((gv + f(1)) / f(2)) * f(size - 1)
+        return ((gv + f(1)) * f(size) - f(1)) / f(2)
+    ix, iy = unn(gx, W), unn(gy, H)
+    ix, iy = np.where(ix > f(-4), ix, f(-4)), np.where(iy > f(-4), iy, f(-4))
+    ix, iy = np.minimum(ix, f(W + 4)), np.minimum(iy, f(H + 4))
+    fx, fy = np.floor(ix), np.floor(iy)
+    ex, ey = fx + f(1), fy + f(1)
+    w = np.stack([(ex - ix) * (ey - iy), (ix - fx) * (ey - iy), (ex - ix) * (iy - fy), (ix - fx) * (iy - fy)], axis=-1)
+    assert w.dtype == np.float32
+    return fx.astype(np.int64), fy.astype(np.int64), w
+
+
+def apply_f32(case, ops=None, fma=False):
+    """The kernels' arithmetic restated in numpy float32 in their order: y = v * s + t (fma: one rounding), relu, + residual, then per warp wsum = 0; wsum += src * w over the valid taps nw, ne, sw, se (fma alike); y += wsum."""
+    o = ops or apply_operands(case)
+    N, H, W, C = case.N, case.H, case.W, case.C
+    f = np.float32
+    mul_add = (lambda a, b, c: (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(f)) if fma \
+        else (lambda a, b, c: (a * b).astype(f) + c)
+    v = o["raw"].numpy()
+    s, t = o["ss"][:, None, None, :, 0].numpy(), o["ss"][:, None, None, :, 1].numpy()
+    y = mul_add(v, np.broadcast_to(s, v.shape), np.broadcast_to(t, v.shape))
+    if case.relu:
+        y = np.maximum(y, f(0))
+    if o["res"] is not None:
+        y = y + o["res"].numpy()
+    for src, flow in o["warps"]:
+        x0, y0, w = grid_taps_f32(flow, H, W, case.align)
+        sn = src.numpy()
+        wsum = np.zeros_like(y)
+        nidx = np.arange(N)[:, None, None] if src.shape[0] > 1 else np.zeros((N, 1, 1), dtype=np.int64)
+        for k, (dy, dx) in enumerate(((0, 0), (0, 1), (1, 0), (1, 1))):
+            yy, xx = y0 + dy, x0 + dx
+            valid = (yy >= 0) & (yy < H) & (xx >= 0) & (xx < W)
+            tap = sn[nidx, np.clip(yy, 0, H - 1), np.clip(xx, 0, W - 1)]
+            wk = np.broadcast_to(w[..., k][..., None], tap.shape)
+            wsum = np.where(valid[..., None], mul_add(tap, wk, wsum), wsum)
+        y = y + wsum
+    assert y.dtype == np.float32
+    return torch.from_numpy(y)
+
+
+def apply_layout_mutant(expected, ld, offset, which):
+    """What a (N,H,W,ld) NaN-filled buffer holds after a kernel wrote `expected` (N,H,W,C) at channel `offset` with the right pixel
+    stride (which None) or with C taken for it ('ld_is_c'): the flat pixel p then starts at p * C + offset."""
+    N, H, W, C = expected.shape
+    buf = torch.full((N * H * W * ld,), float("nan"), dtype=expected.dtype)
+    stride = C if which == "ld_is_c" else ld
+    pos = (torch.arange(N * H * W) * stride + offset).view(-1, 1) + torch.arange(C).view(1, -1)
+    buf[pos.reshape(-1)] = expected.reshape(-1)
+    return buf.view(N, H, W, ld)
+
+
+def _apply_cases():
+    cases, seed = {}, 0
+    for family in ("exact", "random"):
+        for (H, W) in ((4, 32), (6, 20)):
+            for C, warps, align, res, relu in (
+                    (8, (), 0, None, 1), (36, ("shared",), 0, "fp32", 1), (64, ("per_sample", "shared"), 1, "fp32", 0),
+                    (32, ("shared", "per_sample"), 1, "split", 1), (96, ("per_sample",), 0, "split", 1), (32, (), 0, None, 0),
+                    (64, ("shared", "shared"), 0, None, 1), (36, ("per_sample", "per_sample"), 1, None, 1)):
+                seed += 1
+                name = "%s %dx%d C%d warps[%s] align %d res %s relu %d" % (family, H, W, C, ",".join(warps), align, res, relu)
+                cases[name] = ApplyCase(family, 3, H, W, C, relu, warps, align, res, seed)
+    return cases
+
+
+APPLY_CASES = _apply_cases()
+
+
+# ---- raw-input consumers (ConvArgs::raw_in): the halo kernels normalise channels >= raw_from of their input themselves
+RAW_INPUT_CASES = [(name, cin, raw_from) for name in ("halo64", "halo128", "halo_tall", "ct_narrow", "ct_wide")
+                   for cin, raw_from in ((64, 0), (64, 32))] + [("halo64", 32, 0)]
+
+
+def raw_input_case(name, cin, ncu=EXACT_NCU):
+    c = norm_case(name, ncu)
+    c.cin = cin
+    return c
+
+
+def raw_input_operands(case, raw_from, seed=0):
+    """x (N,H,W,Cin): channels < raw_from an activation n / 256, |n| <= 511; channels >= raw_from RAW: integers in [-8, 8] / 4.
+    ss (N, Cin - raw_from, 2): scale +-2^e, e in [-3, -1], shift m / 256, |m| <= 255, both signs -- relu(raw * scale + shift) is a
+    multiple of 1/256 below 2 (it needs its lo term).  w = m / 16, |m| <= 8 (PyTorch layout).  Every product of the conv is a
+    multiple of 2^-12 and the sums stay far below 2^24 quanta: the float64 conv rounded to fp32 is the specification."""
+    g = torch.Generator().manual_seed(12000 + seed + raw_from)
+    N, H, W, cin = case.N, case.H, case.W, case.cin
+    x = grid((N, H, W, cin), g, 511, 256.0)
+    x[..., raw_from:] = torch.randint(-8, 9, (N, H, W, cin - raw_from), generator=g).float() / 4
+    nr = cin - raw_from
+    scale = (torch.randint(0, 2, (N, nr), generator=g).float() * 2 - 1) * torch.pow(2.0, torch.randint(-3, 0, (N, nr), generator=g).float())
+    ss = torch.stack([scale, grid((N, nr), g, 255, 256.0)], dim=-1).contiguous()
+    w = grid(case.w_shape(), g, 8, 16.0)
+    return x, ss, w
+
+
+def raw_input_activation(x, ss, raw_from):
+    """the tensor the kernel must multiply, float64 (N,H,W,Cin): relu(x * scale + shift) on the raw channels"""
+    a = x.double().clone()
+    a[..., raw_from:] = (a[..., raw_from:] * ss[:, None, None, :, 0].double() + ss[:, None, None, :, 1].double()).clamp(min=0)
+    return a
+
+
+def raw_input_reference(case, x, ss, w, raw_from, pad_normalised=False):
+    """float64 conv (N,Ho,Wo,Cout) of the activation with ZERO padding.  pad_normalised: the mutant whose out-of-image taps were
+    normalised with the rest -- a padded raw channel contributes relu(shift) instead of 0."""
+    import torch.nn.functional as F
+    a = raw_input_activation(x, ss, raw_from).permute(0, 3, 1, 2)
+    if not pad_normalised:
+        return case.op(a, w).permute(0, 2, 3, 1).contiguous()
+    N, C, H, W = a.shape
+    fill = torch.zeros(N, C, dtype=torch.float64)
+    fill[:, raw_from:] = ss[..., 1].double().clamp(min=0)
+    if case.transposed:
+        ap = fill[:, :, None, None].expand(N, C, H + 1, W + 1).clone()
+        ap[:, :, :H, :W] = a
+        y = F.conv_transpose2d(ap, w.double(), stride=2, padding=1, output_padding=1)[:, :, :2 * H, :2 * W]
+    else:
+        p = case.pad
+        ap = fill[:, :, None, None].expand(N, C, H + 2 * p, W + 2 * p).clone()
+        ap[:, :, p:p + H, p:p + W] = a
+        y = F.conv2d(ap, w.double(), None, case.stride, 0)
+    return y.permute(0, 2, 3, 1).contiguous()

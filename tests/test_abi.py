@@ -108,6 +108,58 @@ def test_argument_validation_without_a_device():
     assert lib.lwg_conv2d_backward_weight(None, p, p, p, None, p, big, None) == INVALID
     assert wgrad(_Desc(1, 32, 32, 64, 32, 3, 1, 1, 0, 1)) == UNSUPPORTED and b"multiple of 64" in lib.lwg_last_error()
     assert wgrad(_Desc(1, 32, 32, 32, 64, 3, 2, 1, 1, 0)) == UNSUPPORTED      # transposed: Cin is the gradient side
+    # lwg_norm_conv_forward (desc, x, w, bn, in_scale_shift, raw_from, y, partials, variant, ws, bytes, stream): NULL arguments,
+    # bad sizes and every refusal of the conv dispatcher come before the first launch
+    nws = lambda d: lib.lwg_norm_conv_workspace_bytes(ctypes.byref(d))
+    nconv = lambda d, x=p, w=p, bn=0, ss=None, raw_from=0, y=p, part=p, ws=p, nb=big: lib.lwg_norm_conv_forward(
+        ctypes.byref(d), x, w, bn, ss, raw_from, y, part, None, ws, nb, None)
+    halo = _Desc(1, 4, 32, 32, 64, 3, 1, 1, 0, 1)
+    assert lib.lwg_norm_conv_workspace_bytes(None) == 0 and nws(_Desc(1, 4, 32, 24, 64, 3, 1, 1, 0, 1)) == 0
+    assert big >= nws(halo) > 0 and nws(halo) == nws(_Desc(1, 4, 32, 32, 64, 3, 1, 1, 0, 0))
+    for kw in (dict(x=None), dict(w=None), dict(y=None), dict(part=None), dict(ws=None)):
+        assert nconv(halo, **kw) == INVALID and b"NULL" in lib.lwg_last_error(), kw
+    assert lib.lwg_norm_conv_forward(None, p, p, 0, None, 0, p, p, None, p, big, None) == INVALID
+    for kw in (dict(bn=16), dict(bn=-1), dict(x=ctypes.c_void_p(4104)), dict(ws=ctypes.c_void_p(4104)), dict(ss=ctypes.c_void_p(4100))):
+        assert nconv(halo, **kw) == INVALID, kw
+    assert nconv(_Desc(1, 4, 32, 32, 64, 3, 1, 1, 0, 2)) == INVALID                    # no such precision
+    assert nconv(_Desc(0, 4, 32, 32, 64, 3, 1, 1, 0, 1)) == INVALID                    # empty batch
+    assert nconv(halo, nb=nws(halo) - 1) == WORKSPACE
+    assert nconv(_Desc(1, 10, 10, 32, 64, 3, 1, 1, 0, 0)) == UNSUPPORTED and b"128" in lib.lwg_last_error()   # not whole tiles
+    assert nconv(_Desc(1, 4, 32, 32, 96, 3, 1, 1, 0, 1)) == UNSUPPORTED                # Cout not a power of two
+    assert nconv(_Desc(1, 4, 32, 32, 64, 3, 1, 1, 0, 1), bn=128) == UNSUPPORTED        # Cout 64 on the 128-channel tile
+    assert nconv(_Desc(1, 4, 32, 32, 64, 3, 1, 1, 0, 1), bn=32) == UNSUPPORTED         # 32-channel tiles: exact fp32 only
+    assert nconv(_Desc(1, 16, 16, 8, 64, 7, 1, 3, 0, 1)) == UNSUPPORTED                # bf16x3 needs Cin % 32 == 0
+    assert nconv(_Desc(1, 16, 16, 8, 64, 7, 1, 3, 0, 0), bn=128) == UNSUPPORTED        # small Cin: 64-channel tile only
+    raw64 = _Desc(1, 4, 32, 64, 64, 3, 1, 1, 0, 1)
+    assert nconv(raw64, ss=p, raw_from=16) == UNSUPPORTED and b"raw" in lib.lwg_last_error()   # not a 32-channel boundary
+    assert nconv(raw64, ss=p, raw_from=64) == UNSUPPORTED and nconv(raw64, ss=p, raw_from=-32) == UNSUPPORTED
+    assert nconv(_Desc(1, 4, 32, 64, 64, 1, 1, 0, 0, 1), ss=p, raw_from=0) == UNSUPPORTED      # 1x1: the ring kernel takes no raw input
+    assert nconv(_Desc(1, 4, 32, 64, 64, 3, 1, 1, 0, 0), ss=p, raw_from=0) == UNSUPPORTED      # nor does exact fp32
+    # lwg_norm_finalize (partials, nphase, mtiles, N, C, gamma, beta, eps, scale_shift, stream)
+    fin = lambda part=p, nphase=1, mtiles=6, n=3, c=64, gamma=p, beta=p, eps=1e-5, ss=p: lib.lwg_norm_finalize(
+        part, nphase, mtiles, n, c, gamma, beta, eps, ss, None)
+    for kw in (dict(part=None), dict(gamma=None), dict(beta=None), dict(ss=None)):
+        assert fin(**kw) == INVALID and b"NULL" in lib.lwg_last_error(), kw
+    for kw in (dict(nphase=0), dict(nphase=5), dict(mtiles=0), dict(n=0), dict(c=0), dict(eps=-1.0), dict(part=ctypes.c_void_p(4100)),
+               dict(ss=ctypes.c_void_p(4100))):
+        assert fin(**kw) == INVALID, kw
+    assert fin(mtiles=7) == UNSUPPORTED and b"split over" in lib.lwg_last_error()      # tiles of an image are whole
+    # lwg_norm_apply (raw, N, H, W, C, scale_shift, relu, dst, ld_dst, res, ld_res, split, nwarp, src0, n0, T0, src1, n1, T1,
+    # align_corners, lanes, stream)
+    app = lambda raw=p, n=3, h=4, w=32, c=32, ss=p, relu=1, dst=p, ld_dst=32, res=None, ld_res=0, split=0, nwarp=0, s0=None, n0=1, \
+        t0=None, s1=None, n1=1, t1=None, align=0, lanes=0: lib.lwg_norm_apply(
+            raw, n, h, w, c, ss, relu, dst, ld_dst, res, ld_res, split, nwarp, s0, n0, t0, s1, n1, t1, align, lanes, None)
+    for kw in (dict(raw=None), dict(ss=None), dict(dst=None), dict(nwarp=1), dict(nwarp=1, s0=p), dict(nwarp=2, s0=p, t0=p)):
+        assert app(**kw) == INVALID and b"NULL" in lib.lwg_last_error(), kw
+    for kw in (dict(n=0), dict(h=0), dict(w=-1), dict(c=0), dict(nwarp=3), dict(nwarp=-1), dict(lanes=2), dict(split=2), dict(relu=2),
+               dict(align=2), dict(ld_dst=16), dict(res=p, ld_res=16), dict(nwarp=1, s0=p, t0=p, n0=2), dict(nwarp=1, s0=p, t0=p, n0=0),
+               dict(raw=ctypes.c_void_p(4104)), dict(dst=ctypes.c_void_p(4104)), dict(res=ctypes.c_void_p(4104), ld_res=32),
+               dict(nwarp=1, s0=ctypes.c_void_p(4104), t0=p), dict(nwarp=1, s0=p, t0=ctypes.c_void_p(4100))):
+        assert app(**kw) == INVALID, kw
+    for kw in (dict(c=6, ld_dst=8), dict(c=8, ld_dst=10), dict(c=8, ld_dst=8, res=p, ld_res=10), dict(lanes=8),
+               dict(split=1, c=16, ld_dst=32), dict(split=1, ld_dst=48), dict(split=1, dst=ctypes.c_void_p(4096 + 64)),
+               dict(split=1, res=p, ld_res=48), dict(split=1, res=ctypes.c_void_p(4096 + 64), ld_res=32)):
+        assert app(**kw) == UNSUPPORTED, kw
 
 
 def test_product_path_fails_loudly_without_gpu():
