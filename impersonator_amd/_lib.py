@@ -58,6 +58,11 @@ _PROTOS = {
     "lwg_source_p2verts": (_i, [_vp, _i, _i, _vp, _vp]),
     "lwg_vis_f2pts_workspace_bytes": (_sz, [_i, _i]),
     "lwg_vis_f2pts": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _sz, _vp]),
+    "lwg_face_light": (_i, [_vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp]),
+    "lwg_shade_resolve": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp]),
+    "lwg_silhouette_resolve": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "lwg_face_sampler": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "lwg_extract_tex": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
     "lwg_pack_nhwc": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "lwg_unpack_nchw": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "lwg_generator_create": (_i, [_c.POINTER(_vp), _i, _i, _i, _i, _i, _i]),

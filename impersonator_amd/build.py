@@ -25,6 +25,7 @@ SOURCES = [
     # section 5.1; tests/test_pk_opsel_lint.py checks every source for that form, this removes the packed ops from the kernels
     # that may run underneath the generators altogether).  Same values: packing does not change the arithmetic.
     ("raster.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
+    ("render.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     ("warp.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     ("crop.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     ("imgrid.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),

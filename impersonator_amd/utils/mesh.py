@@ -42,6 +42,21 @@ def compute_barycenter(f2vts):
     return v2 + 0.5 * (f2vts[:, 0] - v2) + 0.5 * (f2vts[:, 1] - v2)
 
 
+def create_uvsampler(uv_mapping_path='assets/pretrains/mapper.txt', tex_size=2):
+    """utils/mesh.py:528-566: the static UV sampling grid of SMPLRenderer.forward(dynamic=False), (F, tex_size**2, 2) in
+    [-1,1]: per face the UV points v2 + (v0 - v2) * a + (v1 - v2) * b for a, b in arange(tex_size) / (tex_size - 1) (a the slow
+    index), clipped to the unit square (v flipped)."""
+    if tex_size < 2:
+        raise ValueError("create_uvsampler needs tex_size >= 2 (got %d): the step is 1 / (tex_size - 1)" % tex_size)
+    ab = np.arange(tex_size, dtype=np.float32) / (tex_size - 1)
+    coords = np.stack([np.repeat(ab, tex_size), np.tile(ab, tex_size)], axis=1).T     # (2, T*T), a view of (T*T, 2)
+    f2vts = get_f2vts(uv_mapping_path)[:, :, 0:2]                                     # (F, 3, 2)
+    v2 = f2vts[:, 2]
+    edges = np.stack([f2vts[:, 0] - v2, f2vts[:, 1] - v2], axis=-1)                   # (F, 2, 2): columns v0-v2, v1-v2
+    samples = np.clip(edges.dot(coords) + v2.reshape(-1, 2, 1), 0.0, 1.0)             # (F, 2, T*T)
+    return np.transpose(samples, (0, 2, 1)) * 2 - 1
+
+
 def _face_list(path, nf, fill_back):
     with open(path, 'r') as reader:
         faces = list(json.load(reader)['face'])

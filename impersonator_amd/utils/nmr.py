@@ -3,9 +3,17 @@
 Keeps the method names, argument order and return types of the methods on the Imitator.forward()
 path -- `render_fim_wim`, `encode_fim`, `encode_front_fim`, `cal_bc_transform`, `get_vis_f2pts` --
 and adds `transfer()`, the fused per-frame sequence of models/imitator.py:250-260.
-The textured-rendering half of the reference class (forward/render/extract_tex, lighting) is not used
-by Liquid-Warping-Block inference and is not provided.
+
+The textured-rendering half (utils/nmr.py:179-244,295-310,354-504,587-615,661-662) -- `render`, `forward`,
+`render_silhouettes`, `extract_tex`, `extract_tex_from_image`, `dynamic_sampler`, the light / background / texture-size
+setters and the small tensor helpers -- draws the posed mesh: Liquid-Warping-Block inference does not use it, checking
+an SMPL estimate by eye and the texture-warping baseline (W_T) do.  Forward only (no gradient of the renderer).  It runs
+the rasteriser unchanged at the super-sampled size and shades its maps with the kernels of csrc/render.hip.
+Limits the reference has too, reported instead of failing later: `create_coords` raises ValueError for a `tex_size`
+whose `torch.arange(0, 1 + step, step)` does not have `tex_size` entries (1 and 7 among the small sizes), and `render`
+refuses one-texel cubes (the reference's sampling reads texel 1 of them).
 """
+import ctypes
 import math
 import os
 
@@ -34,10 +42,12 @@ class SMPLRenderer(nn.Module):
     def __init__(self, face_path='assets/pretrains/smpl_faces.npy', uv_map_path='assets/pretrains/mapper.txt',
                  map_name='uv_seg', tex_size=3, image_size=256, anti_aliasing=True, fill_back=False,
                  background_color=(0, 0, 0), viewing_angle=30, near=0.1, far=25.0, has_front=False,
-                 faces=None, map_fn=None, front_map_fn=None, back_map_fn=None, align_corners=False):
+                 faces=None, map_fn=None, front_map_fn=None, back_map_fn=None, align_corners=False, uv_sampler=None):
         """Same signature as utils/nmr.py:104-107.  The trailing keyword arguments (extension) supply the
         face list and the face->condition tables directly; without them they are read from `face_path` and
-        from `<uv_map_path stem>_<map_name>.npy` tables (see utils/mesh.py of this package)."""
+        from `<uv_map_path stem>_<map_name>.npy` tables (see utils/mesh.py of this package).  `uv_sampler`
+        (nf, tex_size**2, 2) is the static UV sampling grid of `forward(dynamic=False)`; without it the grid is built
+        from `uv_map_path` when that file exists (mesh.create_uvsampler)."""
         super().__init__()
         self.background_color = background_color
         self.anti_aliasing = anti_aliasing
@@ -74,6 +84,33 @@ class SMPLRenderer(nn.Module):
         else:
             self.front_map_fn = None
 
+        # texture sampling grids (nmr.py:135,146-149).  A tex_size the reference cannot build coords for leaves them unset;
+        # dynamic_sampler then raises create_coords' error.
+        try:
+            coords = self.create_coords(tex_size)
+        except ValueError:
+            coords = None
+        self.register_buffer('coords', coords, persistent=False)
+        if uv_sampler is None and tex_size >= 2 and os.path.exists(uv_map_path):
+            from . import mesh
+            built = mesh.create_uvsampler(uv_map_path, tex_size=tex_size)
+            if built.shape[0] == self.nf:      # the file describes this face list (not so with fill_back or faces=)
+                uv_sampler = built
+        if uv_sampler is not None:
+            uv_sampler = torch.as_tensor(np.ascontiguousarray(uv_sampler)).float().contiguous()
+            if tuple(uv_sampler.shape) != (self.nf, tex_size * tex_size, 2):
+                raise ValueError("uv_sampler must be (nf, tex_size**2, 2) = (%d, %d, 2), got %s"
+                                 % (self.nf, tex_size * tex_size, tuple(uv_sampler.shape)))
+        self.register_buffer('img2uv_sampler', uv_sampler, persistent=False)
+
+        # light (nmr.py:164-170)
+        self.light_intensity_ambient = 1
+        self.light_intensity_directional = 0
+        self.light_color_ambient = [1, 1, 1]
+        self.light_color_directional = [1, 1, 1]
+        self.light_direction = [0, 1, 0]
+        self.rasterizer_eps = 1e-3
+
         self.near = near
         self.far = far
         self.proj_func = orthographic_proj_withz_idrot
@@ -81,6 +118,8 @@ class SMPLRenderer(nn.Module):
         self.eye = [0, 0, -(1. / np.tan(np.radians(self.viewing_angle)) + 1)]  # nmr.py:177
         self._eye_z = float(np.float32(self.eye[2]))
         self._ws = None
+        self._bufs = {}       # render path: f2verts, the super-sampled maps and the light, kept between calls like _ws
+        self._bg = None       # (colour tuple, device) -> its (1,3) device tensor
 
     # ------------------------------------------------------------------ helpers
     @staticmethod
@@ -243,6 +282,236 @@ class SMPLRenderer(nn.Module):
         _lib.check(_lib.load().lwg_mask_compose(_lib.ptr(img), _lib.ptr(mask), int(bool(invert)), _lib.ptr(tail), ct, n, h, w,
                                                 _lib.ptr(out), _lib.stream_ptr()))
         return out
+
+    # ------------------------------------------------------------------ textured rendering (csrc/render.hip)
+    def set_ambient_light(self, int_dir=0.3, int_amb=0.7, direction=(1, 0.5, 1)):
+        """utils/nmr.py:179-183."""
+        self.light_intensity_directional = int_dir
+        self.light_intensity_ambient = int_amb
+        if direction is not None:
+            self.light_direction = direction
+
+    def set_bgcolor(self, color=(-1, -1, -1)):
+        """utils/nmr.py:185-186: a colour triple, or a per-sample (bs,3) tensor."""
+        self.background_color = color
+
+    def set_tex_size(self, tex_size):
+        """utils/nmr.py:188-190.  Also sets `self.tex_size`, which the reference leaves behind (its extract_tex then reshapes
+        with the old size); coords land on the device the module is on."""
+        coords = self.create_coords(tex_size)
+        self.coords = coords.to(self.faces.device)
+        self.tex_size = tex_size
+
+    def debug_textures(self):
+        """utils/nmr.py:661-662: white cubes (nf,ts,ts,ts,3) on the host; `render` takes them with or without a leading 1."""
+        return torch.ones((self.nf, self.tex_size, self.tex_size, self.tex_size, 3), dtype=torch.float32)
+
+    def _buf(self, name, shape, dtype, device):
+        t = self._bufs.get(name)
+        if t is None or tuple(t.shape) != tuple(shape) or t.device != device:
+            t = self._bufs[name] = torch.empty(shape, dtype=dtype, device=device)
+        return t
+
+    def _background(self, bs, device):
+        """(1|bs, 3) device tensor of `background_color`; a colour triple is uploaded once and kept."""
+        bg = self.background_color
+        if torch.is_tensor(bg):
+            bg = self._cuda(bg.to(device))
+            bg = bg[None] if bg.dim() == 1 else bg
+        else:
+            key = (tuple(float(c) for c in np.asarray(bg, dtype=np.float64).reshape(-1)), device)
+            if self._bg is None or self._bg[0] != key:
+                self._bg = (key, torch.tensor([key[0]], dtype=torch.float32).to(device))
+            bg = self._bg[1]
+        if bg.dim() != 2 or bg.shape[1] != 3 or bg.shape[0] not in (1, bs):
+            raise ValueError("background_color must be a colour triple or a (bs,3) tensor, got shape %s" % (tuple(bg.shape),))
+        return bg
+
+    def _raster_scene(self, cam, vertices, faces, size, near, far, want_depth):
+        """project + rasterise at `size` into the module's cached buffers -> (f2verts, fim, wim, depth | None, face list)."""
+        lib = _lib.load()
+        fidx = self._faces_for(faces).to(vertices.device)
+        bs, nv = vertices.shape[:2]
+        nf, dev, st = fidx.shape[0], vertices.device, _lib.stream_ptr()
+        f2verts = self._buf('f2verts', (bs, nf, 3, 3), torch.float32, dev)
+        fim = self._buf('fim', (bs, size, size), torch.int32, dev)
+        wim = self._buf('wim', (bs, size, size, 3), torch.float32, dev)
+        depth = self._buf('depth', (bs, size, size), torch.float32, dev) if want_depth else None
+        _lib.check(lib.lwg_project_faces(_lib.ptr(vertices), _lib.ptr(cam), _lib.ptr(fidx), bs, nv, nf, self._eye_z,
+                                         _lib.ptr(f2verts), st))
+        ws = self._workspace(bs, nf, dev)
+        _lib.check(lib.lwg_rasterize_fim_wim(_lib.ptr(f2verts), bs, nf, size, near, far, _lib.ptr(fim), _lib.ptr(wim),
+                                             _lib.ptr(depth), _lib.ptr(ws), ws.numel(), st))
+        return f2verts, fim, wim, depth, fidx
+
+    @torch.no_grad()
+    def render(self, cam, vertices, textures, faces=None, get_fim=False):
+        """utils/nmr.py:210-244 -> (images (bs,3,is,is), fim int32 (bs,is,is) or None).  textures (bs,nf,ts,ts,ts,3), or with a
+        leading 1 / without the batch axis: one texture set shared by the batch (extension).  Lighting (on the raw vertices),
+        texture sampling, background and the 2x2 average of anti-aliasing are one shading pass over the rasteriser's maps at
+        near / far = self.near / self.far; the textures are read, never modified."""
+        lib = _lib.load()
+        cam, vertices, textures = self._cuda(cam), self._cuda(vertices), self._cuda(textures)
+        if textures.dim() == 5:
+            textures = textures[None]
+        bs, nv = vertices.shape[:2]
+        ts = textures.shape[2] if textures.dim() == 6 else 0
+        if ts < 2:
+            raise ValueError("render needs textures (bs|1, nf, ts, ts, ts, 3) with ts >= 2, got %s (the reference's sampling "
+                             "reads texel 1 of a one-texel cube)" % (tuple(textures.shape),))
+        s, dev, st = self.image_size, vertices.device, _lib.stream_ptr()
+        aa = bool(self.anti_aliasing)
+        f2verts, fim, wim, depth, fidx = self._raster_scene(cam, vertices, faces, s * 2 if aa else s, self.near, self.far, True)
+        nf = fidx.shape[0]
+        if tuple(textures.shape[1:]) != (nf, ts, ts, ts, 3) or textures.shape[0] not in (1, bs):
+            raise ValueError("textures must be (%d|1, %d, ts, ts, ts, 3), got %s" % (bs, nf, tuple(textures.shape)))
+        bg = self._background(bs, dev)
+        light = self._buf('light', (bs, nf, 3), torch.float32, dev)
+        triple = lambda v: (ctypes.c_float * 3)(*[float(c) for c in np.asarray(v, dtype=np.float64).reshape(3)])
+        _lib.check(lib.lwg_face_light(_lib.ptr(vertices), _lib.ptr(fidx), bs, nv, nf, float(self.light_intensity_ambient),
+                                      float(self.light_intensity_directional), triple(self.light_color_ambient),
+                                      triple(self.light_color_directional), triple(self.light_direction), _lib.ptr(light), st))
+        images = torch.empty((bs, 3, s, s), device=dev, dtype=torch.float32)
+        _lib.check(lib.lwg_shade_resolve(_lib.ptr(f2verts), _lib.ptr(fim), _lib.ptr(wim), _lib.ptr(depth), _lib.ptr(textures),
+                                         textures.shape[0], _lib.ptr(light), _lib.ptr(bg), bg.shape[0], bs, nf, s, int(aa), ts,
+                                         float(self.rasterizer_eps), _lib.ptr(images), st))
+        fim1 = None
+        if get_fim:   # nmr.py:241: a second raster at 1x with the same planes
+            fim1 = torch.empty((bs, s, s), device=dev, dtype=torch.int32)
+            wim1 = self._buf('wim1', (bs, s, s, 3), torch.float32, dev)
+            ws = self._workspace(bs, nf, dev)
+            _lib.check(lib.lwg_rasterize_fim_wim(_lib.ptr(f2verts), bs, nf, s, self.near, self.far, _lib.ptr(fim1),
+                                                 _lib.ptr(wim1), None, _lib.ptr(ws), ws.numel(), st))
+        return images, fim1
+
+    @torch.no_grad()
+    def forward(self, cam, vertices, uv_imgs, dynamic=True, get_fim=False):
+        """utils/nmr.py:192-208 -> (images, textures[, fim]).  dynamic: the textures are sampled from `uv_imgs` at the projected
+        mesh itself; otherwise through the static UV grid `img2uv_sampler`."""
+        if dynamic:
+            samplers = self.dynamic_sampler(cam, vertices, None)
+        else:
+            if self.img2uv_sampler is None:
+                raise RuntimeError("forward(dynamic=False) needs the static UV sampling grid: build the renderer with uv_sampler= "
+                                   "or with a uv_map_path that exists (mesh.create_uvsampler)")
+            samplers = self.img2uv_sampler.to(vertices.device)[None].expand(cam.shape[0], -1, -1, -1).contiguous()
+        textures = self.extract_tex(uv_imgs, samplers)
+        images, fim = self.render(cam, vertices, textures, None, get_fim=get_fim)
+        return (images, textures, fim) if get_fim else (images, textures)
+
+    @torch.no_grad()
+    def render_silhouettes(self, cam, vertices, faces=None):
+        """utils/nmr.py:295-310 -> alpha (bs,is,is): coverage at the rasteriser's default planes, averaged over the 2x2
+        sub-pixels with anti-aliasing."""
+        cam, vertices = self._cuda(cam), self._cuda(vertices)
+        bs, s, aa = vertices.shape[0], self.image_size, bool(self.anti_aliasing)
+        _, fim, _, _, _ = self._raster_scene(cam, vertices, faces, s * 2 if aa else s, self.RASTER_NEAR, self.RASTER_FAR, False)
+        alpha = torch.empty((bs, s, s), device=vertices.device, dtype=torch.float32)
+        _lib.check(_lib.load().lwg_silhouette_resolve(_lib.ptr(fim), bs, s, int(aa), _lib.ptr(alpha), _lib.stream_ptr()))
+        return alpha
+
+    def render_depth(self, cam, vertices):
+        raise NotImplementedError      # utils/nmr.py:280-281
+
+    def infer_face_index_map(self, cam, vertices):
+        raise NotImplementedError      # utils/nmr.py:312-313
+
+    @torch.no_grad()
+    def extract_tex_from_image(self, images, cam, vertices):
+        """utils/nmr.py:354-362: per-face texture cubes sampled from `images` (1|bs,3,h,w) under the projected mesh."""
+        return self.extract_tex(images, self.dynamic_sampler(cam, vertices, None))
+
+    @torch.no_grad()
+    def extract_tex(self, uv_img, uv_sampler):
+        """utils/nmr.py:364-380: uv_img (1|bs,3,h,w), uv_sampler (bs,nf,T*T,2) -> (bs,nf,T,T,T,3); F.grid_sample with the
+        renderer's align_corners, repeated along the third texture axis."""
+        uv_img, uv_sampler = self._cuda(uv_img), self._cuda(uv_sampler)
+        t = self.tex_size
+        if uv_sampler.dim() != 4 or uv_sampler.shape[2] != t * t or uv_sampler.shape[3] != 2:
+            raise ValueError("uv_sampler must be (bs, nf, %d, 2) for tex_size %d, got %s" % (t * t, t, tuple(uv_sampler.shape)))
+        bs, nf = uv_sampler.shape[:2]
+        if uv_img.dim() != 4 or uv_img.shape[1] != 3 or uv_img.shape[0] not in (1, bs):
+            raise ValueError("uv_img must be (%d|1, 3, h, w), got %s" % (bs, tuple(uv_img.shape)))
+        tex = torch.empty((bs, nf, t, t, t, 3), device=uv_img.device, dtype=torch.float32)
+        _lib.check(_lib.load().lwg_extract_tex(_lib.ptr(uv_img), uv_img.shape[0], uv_img.shape[2], uv_img.shape[3],
+                                               _lib.ptr(uv_sampler), bs, nf, t, int(self.align_corners), _lib.ptr(tex),
+                                               _lib.stream_ptr()))
+        return tex
+
+    @torch.no_grad()
+    def dynamic_sampler(self, cam, vertices, faces=None):
+        """utils/nmr.py:382-388 -> (bs,nf,T*T,2): batch_orth_proj_idrot, points_to_faces and points_to_sampler in one launch."""
+        if self.coords is None:
+            self.create_coords(self.tex_size)      # raises: the reference cannot build coords for this tex_size either
+        cam, vertices = self._cuda(cam), self._cuda(vertices)
+        fidx = self._faces_for(faces).to(vertices.device)
+        coords = self._cuda(self.coords.to(vertices.device))
+        bs, nv = vertices.shape[:2]
+        nf, tt = fidx.shape[0], coords.shape[1]
+        sampler = torch.empty((bs, nf, tt, 2), device=vertices.device, dtype=torch.float32)
+        _lib.check(_lib.load().lwg_face_sampler(_lib.ptr(cam), _lib.ptr(vertices), _lib.ptr(fidx), _lib.ptr(coords), bs, nv, nf,
+                                                tt, _lib.ptr(sampler), _lib.stream_ptr()))
+        return sampler
+
+    # the reference's small tensor helpers, as plain torch (any device)
+    def project_to_image(self, cam, vertices):
+        """utils/nmr.py:390-396: the projected x, y without the y flip."""
+        return self.proj_func(vertices, cam)[:, :, 0:2]
+
+    def points_to_faces(self, points, faces=None):
+        """utils/nmr.py:398-415: points (bs,nv,2), faces (bs,nf,3) or the renderer's own -> (bs,nf,3,2)."""
+        bs = points.shape[0]
+        if faces is None:
+            faces = self.faces[None].expand(bs, -1, -1)
+        idx = faces.long().to(points.device)
+        return torch.stack([points[b][idx[b]] for b in range(bs)], dim=0)
+
+    @staticmethod
+    def compute_barycenter(f2vts):
+        """utils/nmr.py:417-432: (N,F,3,2) -> (N,F,2), v2 + (v0 - v2)/2 + (v1 - v2)/2."""
+        v0, v1, v2 = f2vts[:, :, 0], f2vts[:, :, 1], f2vts[:, :, 2]
+        return v2 + 0.5 * (v0 - v2) + 0.5 * (v1 - v2)
+
+    @staticmethod
+    def batch_orth_proj_idrot(camera, X):
+        """utils/nmr.py:434-449: camera (N,3), X (N,P,3) -> s * (X_xy + t), (N,P,2)."""
+        return camera[:, None, 0:1] * (X[:, :, :2] + camera[:, None, 1:])
+
+    @staticmethod
+    def points_to_sampler(coords, faces):
+        """utils/nmr.py:451-470: coords (2,T*T), faces (bs,nf,3,2) -> (bs,nf,T*T,2) in [-1,1]."""
+        v2 = faces[:, :, 2]
+        edges = torch.stack((faces[:, :, 0] - v2, faces[:, :, 1] - v2), dim=-1)      # (bs,nf,2,2)
+        samples = torch.matmul(edges, coords) + v2[..., None]                      # (bs,nf,2,T*T)
+        return samples.permute(0, 1, 3, 2).clamp(min=-1.0, max=1.0)
+
+    @staticmethod
+    def create_coords(tex_size=3):
+        """utils/nmr.py:472-488 -> (2, tex_size**2) barycentric sample points, on the host.  The reference's
+        `torch.arange(0, 1 + step, step)` is kept; where its length is not tex_size (the end point is or is not reached in
+        float arithmetic: tex_size 1 and 7 among the small sizes) every later reshape of the reference fails, so: ValueError."""
+        step = 1 if tex_size == 1 else 1 / (tex_size - 1)
+        alpha_beta = torch.arange(0, 1 + step, step, dtype=torch.float32)
+        if alpha_beta.numel() != tex_size:
+            raise ValueError("tex_size %d is not usable: arange(0, 1 + step, step) has %d entries" % (tex_size, alpha_beta.numel()))
+        xv, yv = torch.meshgrid([alpha_beta, alpha_beta], indexing='ij')
+        return torch.stack([xv.flatten(), yv.flatten()], dim=0)
+
+    @staticmethod
+    def create_meshgrid(image_size):
+        """utils/nmr.py:490-504 -> (is,is,2) pixel grid in [-1,1], last axis (x, y)."""
+        factor = (torch.arange(0, image_size, dtype=torch.float32) / (image_size - 1) - 0.5) * 2
+        xv, yv = torch.meshgrid([factor, factor], indexing='ij')
+        return torch.stack([yv, xv], dim=-1)
+
+    def cal_transform(self, bc_f2pts, src_fim, dst_fim):
+        """utils/nmr.py:587-615: T (bs,is,is,2) = bc_f2pts[b, dst_fim] on covered pixels, -2 elsewhere."""
+        bs = src_fim.shape[0]
+        T = torch.zeros(bs, self.image_size, self.image_size, 2, device=bc_f2pts.device) - 2
+        for i in range(bs):
+            covered = dst_fim[i] != -1
+            T[i][covered] = bc_f2pts[i, dst_fim[i][covered].long()]
+        return T
 
     # ------------------------------------------------------------------ fused per-frame path
     @torch.no_grad()

@@ -232,6 +232,39 @@ LWG_API size_t lwg_vis_f2pts_workspace_bytes(int bs, int nf);
 LWG_API int lwg_vis_f2pts(const float *f2pts, int bs, int nf, int per_face, const int32_t *fim, int H, int W, float *out,
                           void *workspace, size_t workspace_bytes, lwg_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Textured rendering (render.hip): the shading half of SMPLRenderer (utils/nmr.py:192-244,295-310,354-388) on top of
+ * lwg_project_faces + lwg_rasterize_fim_wim.  Forward only.
+ * face_light: neural_renderer/lighting.py:33-53 per face on the RAW vertices: verts (bs,nv,3), faces_idx (nf,3) ->
+ *   light (bs,nf,3) = int_amb * color_amb + int_dir * color_dir * relu(dot(n, direction)), n = cross(v0-v1, v2-v1) /
+ *   max(|cross|, 1e-5); direction is used as given; a term whose intensity is 0 is skipped.  The three colour / direction
+ *   triples are HOST pointers.
+ * shade_resolve: rasterize_cuda_kernel.cu:207-259 + rasterize.py:190-197 + :343.  f2verts (bs,nf,3,3); fim / wim / depth as
+ *   lwg_rasterize_fim_wim writes them at S = image_size * (anti_aliasing ? 2 : 1); textures (tex_bs,nf,ts,ts,ts,3) and
+ *   background (bg_bs,3) with a batch of 1 (shared) or bs; light (bs,nf,3) -> rgb (bs,3,image_size,image_size).  Covered
+ *   sub-pixels (0 <= fim < nf) take the eight-corner blend at tif[k] = w[k] * (ts-1) * (depth / z_k) clamped to
+ *   [0, (ts-1) - eps], times the face's light; the others the background; anti_aliasing averages the 2x2 sub-pixels.
+ *   tex_size >= 2.
+ * silhouette_resolve: fim at S -> alpha (bs,image_size,image_size): fim >= 0, averaged over 2x2 with anti_aliasing.
+ * face_sampler: SMPLRenderer.dynamic_sampler (nmr.py:382-388): p = s * (X_xy + t) (no y flip), then per face and per column
+ *   t of coords (2,tex_points): (v0-v2) * c0 + (v1-v2) * c1 + v2 clamped to [-1,1] -> sampler (bs,nf,tex_points,2).
+ * extract_tex: SMPLRenderer.extract_tex (nmr.py:364-380): uv_img (img_bs,3,H,W), img_bs 1 or bs; sampler (bs,nf,ts*ts,2)
+ *   -> tex (bs,nf,ts,ts,ts,3), the bilinear sample (bit-identical to lwg_grid_sample on the same grid) repeated along the
+ *   third texture axis. */
+LWG_API int lwg_face_light(const float *verts, const int32_t *faces_idx, int bs, int nv, int nf, float intensity_ambient,
+                           float intensity_directional, const float *color_ambient_host, const float *color_directional_host,
+                           const float *direction_host, float *light, lwg_stream_t stream);
+LWG_API int lwg_shade_resolve(const float *f2verts, const int32_t *fim, const float *wim, const float *depth,
+                              const float *textures, int tex_bs, const float *light, const float *background, int bg_bs, int bs,
+                              int nf, int image_size, int anti_aliasing, int tex_size, float eps, float *rgb,
+                              lwg_stream_t stream);
+LWG_API int lwg_silhouette_resolve(const int32_t *fim, int bs, int image_size, int anti_aliasing, float *alpha,
+                                   lwg_stream_t stream);
+LWG_API int lwg_face_sampler(const float *cam, const float *verts, const int32_t *faces_idx, const float *coords, int bs, int nv,
+                             int nf, int tex_points, float *sampler, lwg_stream_t stream);
+LWG_API int lwg_extract_tex(const float *uv_img, int img_bs, int H, int W, const float *sampler, int bs, int nf, int tex_size,
+                            int align_corners, float *tex, lwg_stream_t stream);
+
 /* NCHW (n,C,H,W) -> NHWC with the channel count padded to cpad (zeros), and back (first C channels). */
 LWG_API int lwg_pack_nhwc(const float *x_nchw, int n, int C, int H, int W, int cpad, float *out_nhwc,
                           lwg_stream_t stream);
