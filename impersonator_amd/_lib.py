@@ -50,6 +50,9 @@ _PROTOS = {
     "lwg_rigid_views": (_i, [_vp, _c.c_long, _vp, _i, _vp, _vp]),
     "lwg_image_grid_shape": (_i, [_i, _i, _i, _i, _i, _c.POINTER(_i), _c.POINTER(_i)]),
     "lwg_image_grid_u8": (_i, [_vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp]),
+    "lwg_jpeg_stream_bytes": (_sz, [_i, _i, _i]),
+    "lwg_jpeg_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "lwg_jpeg_encode": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _sz, _vp]),
     "lwg_smpl_workspace_bytes": (_sz, [_i]),
     "lwg_smpl_forward": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "lwg_smpl_forward_f64": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -29,6 +29,7 @@ SOURCES = [
     ("warp.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     ("crop.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     ("imgrid.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
+    ("jpeg.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     ("smpl.hip", ["-fno-slp-vectorize"]),
     ("personalize.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     ("animate.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),

@@ -176,7 +176,8 @@ class Animator(Swapper):
         return self.forward(tsf_inputs, self.tsf_info['T'])
 
     @torch.no_grad()
-    def animate(self, tgt_paths, tgt_smpls=None, cam_strategy='smooth', target_part='body', output_dir='', visualizer=None):
+    def animate(self, tgt_paths, tgt_smpls=None, cam_strategy='smooth', target_part='body', output_dir='', visualizer=None,
+                device_jpeg=False, jpeg_quality=75, jpeg_subsampling='4:2:0'):
         """-> list of (H,W,3) float arrays in [-1,1], like Imitator.inference: the frames in batches of `opt.batch_size` through
         `predict_batches`.  Without `tgt_smpls` the SMPL vectors come from the HMR regressor (needs an --hmr_model checkpoint)."""
         self.set_target_part(target_part)
@@ -192,4 +193,10 @@ class Animator(Swapper):
                 filename = os.path.split(tgt_paths[t])[-1] if tgt_paths and tgt_paths[t] else '%.8d.jpg' % t
                 cv_utils.save_cv2_img(pred, os.path.join(output_dir, 'pred_' + filename), normalize=True)
 
+        if device_jpeg and output_dir:
+            # the frames are encoded on the device and written under the same names; the written paths are returned
+            name = lambda t: 'pred_' + (self._jpg_name(os.path.split(tgt_paths[t])[-1]) if tgt_paths and tgt_paths[t]
+                                        else '%.8d.jpg' % t)
+            return self._run_batches(tgt_smpls, cam_strategy, None, self._jpeg_sink(output_dir, name, visualizer, cam_strategy),
+                                     dict(quality=jpeg_quality, subsampling=jpeg_subsampling))
         return self._run_batches(tgt_smpls, cam_strategy, sink)

@@ -550,7 +550,10 @@ class Imitator(BaseModel):
             main.wait_stream(side)
 
     # ------------------------------------------------------------------ drivers (imitator.py:157-214)
-    def _run_batches(self, tgt_smpls, cam_strategy, on_batch):
+    def _run_batches(self, tgt_smpls, cam_strategy, on_batch, on_bytes=None, jpeg=None):
+        """`on_batch(t, host_frame, device_frame)` per frame, after one float device->host copy per batch; returns the frames.
+        With `on_bytes(t, jpg_bytes, device_frame)` instead (a byte sink): every batch is encoded on the device with the
+        `jpeg` keywords of util.jpeg_bytes, only the finished streams come to the host, and the sink's results are returned."""
         if len(tgt_smpls) == 0:      # the reference's loop over range(0) (imitator.py:166,196): nothing to do
             return []
         if not torch.is_tensor(tgt_smpls) and all(torch.is_tensor(t) for t in tgt_smpls):
@@ -565,6 +568,10 @@ class Imitator(BaseModel):
             self.first_cam = smpls[0:1, 0:3].clone().cuda()
         smpls = smpls.cuda()
         for s, preds in self.predict_batches(((smpls[s:s + bs], s) for s in range(0, len(smpls), bs)), cam_strategy):
+            if on_bytes is not None:
+                for i, data in enumerate(util.jpeg_bytes(preds, **(jpeg or {}))):
+                    outputs.append(on_bytes(s + i, data, preds[i:i + 1]))
+                continue
             host = preds.permute(0, 2, 3, 1).cpu().numpy()   # one device->host copy per batch
             for i in range(host.shape[0]):
                 outputs.append(host[i])
@@ -573,8 +580,10 @@ class Imitator(BaseModel):
 
     @torch.no_grad()
     def inference(self, tgt_paths, tgt_smpls=None, cam_strategy='smooth', output_dir='', visualizer=None,
-                  verbose=True):
-        """imitator.py:157-189 -> list of (H,W,3) float arrays in [-1,1]."""
+                  verbose=True, device_jpeg=False, jpeg_quality=75, jpeg_subsampling='4:2:0'):
+        """imitator.py:157-189 -> list of (H,W,3) float arrays in [-1,1].
+        `device_jpeg` (extension) with an `output_dir`: the frames are encoded on the device (util.jpeg_bytes) and written under
+        the same names; no float frame comes to the host and the list of written paths is returned."""
         if tgt_smpls is None:
             if not self._has_regressor():
                 raise NotImplementedError("estimating SMPL from target images needs the HMR regressor; pass tgt_smpls")
@@ -587,17 +596,44 @@ class Imitator(BaseModel):
                 filename = os.path.split(tgt_paths[t])[-1] if tgt_paths and tgt_paths[t] else 'pred_%.8d.jpg' % t
                 cv_utils.save_cv2_img(pred, os.path.join(output_dir, 'pred_' + filename), normalize=True)
 
+        if device_jpeg and output_dir:
+            name = lambda t: 'pred_' + (self._jpg_name(os.path.split(tgt_paths[t])[-1]) if tgt_paths and tgt_paths[t]
+                                        else 'pred_%.8d.jpg' % t)
+            return self._run_batches(tgt_smpls, cam_strategy, None, self._jpeg_sink(output_dir, name, visualizer, cam_strategy),
+                                     dict(quality=jpeg_quality, subsampling=jpeg_subsampling))
         return self._run_batches(tgt_smpls, cam_strategy, sink)
 
+    @staticmethod
+    def _jpg_name(filename):
+        """the file name a JPEG stream is written under: `filename`, with `.jpg` in place of any other extension"""
+        stem, ext = os.path.splitext(filename)
+        return filename if ext.lower() in ('.jpg', '.jpeg') else stem + '.jpg'
+
+    def _jpeg_sink(self, output_dir, name_of, visualizer, cam_strategy):
+        """byte sink of _run_batches: frame t's stream goes to output_dir/name_of(t) as it is; returns the path"""
+        def sink(t, data, pred_dev):
+            if visualizer is not None:
+                visualizer.vis_named_img('pred_' + cam_strategy, pred_dev)
+            path = os.path.join(output_dir, name_of(t))
+            with open(path, 'wb') as fh:
+                fh.write(data)
+            return path
+        return sink
+
     @torch.no_grad()
-    def inference_by_smpls(self, tgt_smpls, cam_strategy='smooth', output_dir='', visualizer=None):
-        """imitator.py:191-214."""
+    def inference_by_smpls(self, tgt_smpls, cam_strategy='smooth', output_dir='', visualizer=None, device_jpeg=False,
+                           jpeg_quality=75, jpeg_subsampling='4:2:0'):
+        """imitator.py:191-214.  `device_jpeg`, `jpeg_quality`, `jpeg_subsampling`: as in `inference`."""
         def sink(t, pred, pred_dev):
             if visualizer is not None:
                 visualizer.vis_named_img('pred_' + cam_strategy, pred_dev)
             if output_dir:
                 cv_utils.save_cv2_img(pred, os.path.join(output_dir, 'pred_%.8d.jpg' % t), normalize=True)
 
+        if device_jpeg and output_dir:
+            return self._run_batches(tgt_smpls, cam_strategy, None,
+                                     self._jpeg_sink(output_dir, lambda t: 'pred_%.8d.jpg' % t, visualizer, cam_strategy),
+                                     dict(quality=jpeg_quality, subsampling=jpeg_subsampling))
         return self._run_batches(tgt_smpls, cam_strategy, sink)
 
     def post_personalize(self, out_dir, data_loader, visualizer, verbose=True):

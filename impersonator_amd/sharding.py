@@ -113,15 +113,17 @@ def gather_in_frame_order(local_items, num_frames, batch, rank, world):
     return out
 
 
-def imitate_sharded(imitator, tgt_smpls, batch, cam_strategy='smooth', rank=0, world=1):
+def imitate_sharded(imitator, tgt_smpls, batch, cam_strategy='smooth', rank=0, world=1, jpeg_sink=None, jpeg=None):
     """Motion imitation of a whole sequence on `world` ranks (what run_imitator.py runs; the reference loops frames on
     one device, models/imitator.py:157-214): this rank pushes its round-robin blocks through
     Imitator.predict_batches (geometry stream + generator lanes), results go to the host once per block, and rank 0
     gets the (H,W,3) frames of ALL ranks in frame order (None elsewhere).  `first_cam` is frame 0's camera on every
-    rank (the reference discovers it at t == 0, imitator.py:243-244).  No data-path collective."""
+    rank (the reference discovers it at t == 0, imitator.py:243-244).  No data-path collective.
+    With `jpeg_sink(t, jpg_bytes)`: every rank encodes ITS frames on the device (util.jpeg_bytes with the `jpeg` keywords) and
+    hands each stream to the sink; nothing is gathered and the sink's results for this rank's frames are returned."""
     import numpy as np
     if len(tgt_smpls) == 0:
-        return [] if rank == 0 else None
+        return [] if rank == 0 or jpeg_sink is not None else None
     smpls = torch.as_tensor(np.asarray(tgt_smpls), dtype=torch.float32).reshape(len(tgt_smpls), -1).cuda()
     n = smpls.shape[0]
     if cam_strategy == 'smooth' and n:
@@ -133,6 +135,11 @@ def imitate_sharded(imitator, tgt_smpls, batch, cam_strategy='smooth', rank=0, w
     # t = 0 would re-derive first_cam from the chunk, which is only right for the block that starts the sequence
     chunks = ((mine[a:b], s) for (a, b), (s, _) in zip(bounds, blocks))
     local = []
+    if jpeg_sink is not None:
+        from .utils import util
+        for s, preds in imitator.predict_batches(chunks, cam_strategy):
+            local += [jpeg_sink(s + i, data) for i, data in enumerate(util.jpeg_bytes(preds, **(jpeg or {})))]
+        return local
     for _, preds in imitator.predict_batches(chunks, cam_strategy):
         local += list(preds.permute(0, 2, 3, 1).cpu().numpy())
     return gather_in_frame_order(local, n, batch, rank, world)

@@ -71,6 +71,57 @@ def save_image_grid(x, path, nrow=8, padding=2, pad_value=0.0, normalize=False):
     return grid
 
 
+_JPEG_SUBSAMPLING = {'4:2:0': 420, '420': 420, 420: 420, '4:4:4': 444, '444': 444, 444: 444}
+
+
+def _jpeg_subsampling(subsampling):
+    try:
+        return _JPEG_SUBSAMPLING[subsampling]
+    except (KeyError, TypeError):
+        raise ValueError("jpeg subsampling %r: '4:2:0' (420) or '4:4:4' (444) expected" % (subsampling,))
+
+
+def jpeg_stream_bytes(H, W, subsampling='4:2:0'):
+    """The most one frame's .jpg stream can take (lwg_jpeg_stream_bytes; needs no device): the row stride of jpeg_encode."""
+    from .. import _lib
+    n = _lib.load().lwg_jpeg_stream_bytes(int(H), int(W), _jpeg_subsampling(subsampling))
+    if n == 0:
+        raise ValueError("jpeg: %d x %d: sides must be positive multiples of 16" % (H, W))
+    return n
+
+
+def jpeg_encode(x, quality=75, subsampling='4:2:0'):
+    """Baseline JPEG files of a batch of images, encoded on the device (lwg_jpeg_encode, csrc/jpeg.hip): x (N,3,H,W) CUDA float
+    tensor in [-1,1] -> (bytes uint8 (N, stride), lengths int32 (N,)), both CUDA tensors; frame n's file is bytes[n, :lengths[n]]
+    and equals what PIL writes (`quality`, `subsampling`, optimize=False) for the uint8 image of cv_utils.save_cv2_img(normalize=True).
+    Stream-ordered, no synchronisation; H and W must be multiples of 16."""
+    from .. import _lib
+    if not x.is_cuda:
+        raise RuntimeError("jpeg_encode: the images must be a CUDA tensor (no CPU path)")
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError("jpeg_encode: (n, 3, H, W) expected, got %s" % (tuple(x.shape),))
+    sub = _jpeg_subsampling(subsampling)
+    x = x.float().contiguous()
+    n, _, h, w = x.shape
+    lib = _lib.load()
+    stride, ws_bytes = lib.lwg_jpeg_stream_bytes(h, w, sub), lib.lwg_jpeg_workspace_bytes(n, h, w, sub)
+    out = torch.empty((n, max(stride, 1)), device=x.device, dtype=torch.uint8)
+    lengths = torch.empty((n,), device=x.device, dtype=torch.int32)
+    ws = torch.empty((max(ws_bytes, 16),), device=x.device, dtype=torch.uint8)
+    _lib.check(lib.lwg_jpeg_encode(_lib.ptr(x), n, h, w, int(quality), sub, _lib.ptr(out), out.stride(0), _lib.ptr(lengths),
+                                   _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
+    return out, lengths
+
+
+def jpeg_bytes(x, quality=75, subsampling='4:2:0'):
+    """jpeg_encode, then the files as a list of `bytes`: the lengths come to the host first, then only out[:, :max(lengths)]
+    (about 13 KB a frame at 256 x 256 and quality 75, against 786 KB of float32), sliced per frame on the host."""
+    out, lengths = jpeg_encode(x, quality=quality, subsampling=subsampling)
+    lens = lengths.cpu().tolist()
+    host = out[:, :max(lens)].cpu().numpy()
+    return [host[i, :n].tobytes() for i, n in enumerate(lens)]
+
+
 def load_pickle_file(pkl_path):
     """utils/util.py:235-239."""
     with open(pkl_path, 'rb') as f:

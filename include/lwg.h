@@ -210,6 +210,22 @@ LWG_API int lwg_animate_inputs(const int32_t *fim, const float *wim, int bs, int
 LWG_API int lwg_image_grid_shape(int n, int H, int W, int nrow, int padding, int *grid_h, int *grid_w);
 LWG_API int lwg_image_grid_u8(const float *x, int n, int H, int W, int nrow, int padding, float pad_value, int normalize,
                               unsigned char *out, lwg_stream_t stream);
+/* Baseline sequential JFIF (JPEG) encoder: x (N,3,H,W) fp32 NCHW in [-1,1] -- what Imitator.forward returns -- -> N finished
+ * .jpg streams, byte-identical to libjpeg's baseline encoder with its default Huffman tables on the uint8 image
+ * trunc(((x + 1) / 2) * 255) (utils/cv_utils.py: save_cv2_img, normalize=True; clamped, NaN -> 0).  The algorithm is stated in
+ * csrc/jpeg.hip.  Frame n's stream is out[n * row_stride ... + lengths[n]); bytes behind it are unspecified.
+ *   subsampling: 420 (4:2:0) or 444 (4:4:4); quality 1..100 (libjpeg's scaling of the Annex K tables).
+ *   lwg_jpeg_stream_bytes: the most a stream can take, 623 + 2 * ceil(nblocks * 1658 / 8) + 2 (a block emits at most 1658 bits,
+ *     every byte may be stuffed) -- the least row_stride; lwg_jpeg_workspace_bytes: scratch of one call.  Both need no device and
+ *     return 0 for sizes lwg_jpeg_encode refuses.
+ *   Stream-ordered: no host synchronisation, no host-to-device copy (capturable in a graph); deterministic byte for byte.
+ * NULL pointers, N / H / W <= 0, quality outside 1..100, an unknown subsampling, x or lengths not 4-byte or the workspace not
+ * 16-byte aligned: LWG_ERR_INVALID_ARG; H or W not a multiple of 16: LWG_ERR_UNSUPPORTED; a short workspace or row_stride:
+ * LWG_ERR_WORKSPACE -- all before the first HIP call. */
+LWG_API size_t lwg_jpeg_stream_bytes(int H, int W, int subsampling);
+LWG_API size_t lwg_jpeg_workspace_bytes(int N, int H, int W, int subsampling);
+LWG_API int lwg_jpeg_encode(const float *x, int N, int H, int W, int quality, int subsampling, uint8_t *out, size_t row_stride,
+                            int32_t *lengths, void *workspace, size_t workspace_bytes, lwg_stream_t stream);
 /* ---- Once-per-source glue of Imitator.personalize (models/imitator.py:82-155), so that `personalize` launches no
  * framework kernel.
  * morph: utils/util.py:73-89 -- erode (mode 0: pad with 1, count == ks*ks) / dilate (mode 1: pad with 0, count >= 1) of a

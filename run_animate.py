@@ -18,12 +18,21 @@ sys.path.insert(0, ROOT)
 
 from impersonator_amd import demo  # noqa: E402
 from impersonator_amd.options.animate_options import AnimateOptions  # noqa: E402
+from impersonator_amd.options.jpeg_options import add_jpeg_arguments  # noqa: E402
 from impersonator_amd.utils import synthetic, util  # noqa: E402
 from run_imitator import _target_smpls, scan_tgt_paths  # noqa: E402
 
 
+class AnimateJpegOptions(AnimateOptions):
+    """AnimateOptions + the flags of the device JPEG writer (--device_jpeg, --jpeg_quality, --jpeg_subsampling)"""
+
+    def initialize(self):
+        super().initialize()
+        add_jpeg_arguments(self._parser)
+
+
 def main():
-    opt = AnimateOptions().parse()
+    opt = AnimateJpegOptions().parse()
     torch.cuda.set_device(0)
     if opt.synthetic:
         an, smpl_a, img_a, bg_a = demo.build_synthetic_imitator(
@@ -44,7 +53,8 @@ def main():
         tgt_paths = scan_tgt_paths(opt.tgt_path, itv=1)
         tgt_smpls = _target_smpls(an, tgt_paths)
     out_dir = util.mkdir(os.path.join(opt.output_dir, 'animators')) if opt.save_res else ''
-    outs = an.animate(tgt_paths, tgt_smpls=tgt_smpls, cam_strategy=opt.cam_strategy, target_part=opt.swap_part, output_dir=out_dir)
+    outs = an.animate(tgt_paths, tgt_smpls=tgt_smpls, cam_strategy=opt.cam_strategy, target_part=opt.swap_part, output_dir=out_dir,
+                      device_jpeg=opt.device_jpeg, jpeg_quality=opt.jpeg_quality, jpeg_subsampling=opt.jpeg_subsampling)
     if out_dir:
         print('Saving %d frames to %s' % (len(outs), out_dir))
 

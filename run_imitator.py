@@ -8,6 +8,8 @@
     python run_imitator.py --synthetic --hmr_model H.pth --src_path S.jpg --tgt_path DIR --output_dir OUT
                                                       (synthetic body model and generator, SMPLs estimated from the images)
     python run_imitator.py ... --post_tune --pri_path DIR     (personalise by fine-tuning first: adaptive_personalize)
+    python run_imitator.py ... --device_jpeg [--jpeg_quality 75] [--jpeg_subsampling 420] [--save_video OUT.avi]
+                                                      (frames encoded as JPEG on the device; the streams also as one MJPG .avi)
 
 When `--hmr_model` names a checkpoint of the HMR regressor (the reference's hmr_tf2pt.pth, or one saved from
 `utils.synthetic.hmr_state_dict`), the SMPL parameters of source and targets are estimated from the images as the reference
@@ -24,7 +26,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 from impersonator_amd import demo, sharding  # noqa: E402
-from impersonator_amd.options.test_options import TestOptions  # noqa: E402
+from impersonator_amd.options.jpeg_options import JpegOptions  # noqa: E402
 from impersonator_amd.utils import cv_utils, util  # noqa: E402
 
 
@@ -75,8 +77,37 @@ def adaptive_personalize(opt, imitator, visualizer=None):
     return imitator.post_personalize(opt.output_dir, samples, visualizer=visualizer, verbose=False)
 
 
+def write_device_jpegs(opt, imitator, tgt_smpls, tgt_paths, rank, world):
+    """--device_jpeg: every rank encodes its own frames on the device and writes the finished streams (no float frame comes to
+    the host, nothing is gathered); named after the target files, `pred_%08d.jpg` for the synthetic sequence.  --save_video:
+    rank 0 then stores the written streams, as they are, in one Motion-JPEG .avi file."""
+    out_dir = util.mkdir(opt.output_dir)
+    name = lambda t: 'pred_' + (imitator._jpg_name(os.path.split(tgt_paths[t])[-1]) if tgt_paths else '%.8d.jpg' % t)
+
+    def sink(t, data):
+        path = os.path.join(out_dir, name(t))
+        with open(path, 'wb') as fh:
+            fh.write(data)
+        return path
+
+    written = sharding.imitate_sharded(imitator, tgt_smpls, opt.batch_size, opt.cam_strategy, rank, world, jpeg_sink=sink,
+                                       jpeg=dict(quality=opt.jpeg_quality, subsampling=opt.jpeg_subsampling))
+    print('wrote %d frames to %s' % (len(written), out_dir) if world == 1 else
+          'rank %d wrote %d frames to %s' % (rank, len(written), out_dir))
+    if opt.save_video:
+        sharding.barrier()
+        if rank == 0:
+            from impersonator_amd.utils.video import write_mjpeg_avi
+            streams = []
+            for t in range(len(tgt_smpls)):
+                with open(os.path.join(out_dir, name(t)), 'rb') as fh:
+                    streams.append(fh.read())
+            write_mjpeg_avi(opt.save_video, streams, opt.fps, (opt.image_size, opt.image_size))
+            print('wrote %d frames to %s' % (len(streams), opt.save_video))
+
+
 def main():
-    opt = TestOptions().parse()
+    opt = JpegOptions().parse()
     rank, local_rank, world = sharding.init_process_group()
     if local_rank >= torch.cuda.device_count() and os.environ.get("LWG_DIST_BACKEND") == "gloo":
         local_rank %= torch.cuda.device_count()   # test hook: N gloo ranks sharing the visible GPU(s) (RCCL wants one each)
@@ -115,6 +146,14 @@ def main():
         adaptive_personalize(opt, imitator, None)
         personalize()            # run_imitator.py:229: once more, on the tuned weights
         print('\n\t\t\tPersonalization: completed...')
+
+    if opt.save_video and not (opt.device_jpeg and opt.output_dir):
+        raise SystemExit('--save_video stores the streams of --device_jpeg: give --device_jpeg and --output_dir too')
+    if opt.device_jpeg and opt.output_dir:
+        write_device_jpegs(opt, imitator, tgt_smpls, tgt_paths, rank, world)
+        if torch.distributed.is_initialized():
+            torch.distributed.destroy_process_group()
+        return
 
     # frame sharding: every rank imitates its own blocks of `batch_size` frames (first_cam = frame 0's camera everywhere)
     outs = sharding.imitate_sharded(imitator, tgt_smpls, opt.batch_size, opt.cam_strategy, rank, world)

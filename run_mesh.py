@@ -24,6 +24,7 @@ import torch
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
+from impersonator_amd.options.jpeg_options import add_jpeg_arguments  # noqa: E402
 from impersonator_amd.options.test_options import TestOptions  # noqa: E402
 from impersonator_amd.utils import cv_utils, synthetic, util  # noqa: E402
 from impersonator_amd.utils.nmr import SMPLRenderer  # noqa: E402
@@ -34,6 +35,7 @@ class MeshOptions(TestOptions):
         super().initialize()
         self._parser.add_argument('--texture_warp', action='store_true', default=False,
                                   help="also render the source's extracted texture on every target pose (wt_*.jpg)")
+        add_jpeg_arguments(self._parser)
 
 
 def save_unit_image(chw, path):
@@ -92,12 +94,20 @@ def main(args=None):
         cam, v, img = cams[s:s + bs].contiguous(), verts[s:s + bs].contiguous(), frames[s:s + bs]
         mesh, _ = render.render(cam, v, white)
         masked = img * render.render_silhouettes(cam, v)[:, None]
-        outs = {'mesh': mesh.cpu().numpy(), 'masked': masked.cpu().numpy()}
+        outs = {'mesh': mesh, 'masked': masked}
         if src_tex is not None:
             render.light_intensity_ambient, render.light_intensity_directional = 1, 0     # the texture carries its own shading
-            outs['wt'] = render.render(cam, v, src_tex)[0].cpu().numpy()
+            outs['wt'] = render.render(cam, v, src_tex)[0]
             render.set_ambient_light()
         for kind, batch in outs.items():
+            if opt.device_jpeg:
+                # encoded on the device: the pictures as [-1,1] images, truncated to uint8 as the other drivers' frames are
+                streams = util.jpeg_bytes(batch.clamp(0, 1) * 2 - 1, quality=opt.jpeg_quality, subsampling=opt.jpeg_subsampling)
+                for k, data in enumerate(streams):
+                    with open(os.path.join(out_dir, '%s_%08d.jpg' % (kind, s - first + k)), 'wb') as fh:
+                        fh.write(data)
+                continue
+            batch = batch.cpu().numpy()
             for k in range(batch.shape[0]):
                 save_unit_image(batch[k], os.path.join(out_dir, '%s_%08d.jpg' % (kind, s - first + k)))
     print('wrote %d frames to %s' % (verts.shape[0] - first, out_dir))
