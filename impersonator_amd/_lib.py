@@ -53,6 +53,10 @@ _PROTOS = {
     "lwg_jpeg_stream_bytes": (_sz, [_i, _i, _i]),
     "lwg_jpeg_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "lwg_jpeg_encode": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _sz, _vp]),
+    "lwg_eval_workspace_bytes": (_sz, [_i, _i, _i]),
+    "lwg_eval_pair_stats": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "lwg_resize_bilinear": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "lwg_eval_sspe_terms": (_i, [_vp, _vp, _i, _vp, _vp]),
     "lwg_smpl_workspace_bytes": (_sz, [_i]),
     "lwg_smpl_forward": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "lwg_smpl_forward_f64": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

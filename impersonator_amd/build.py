@@ -30,6 +30,7 @@ SOURCES = [
     ("crop.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     ("imgrid.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     ("jpeg.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
+    ("eval.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     ("smpl.hip", ["-fno-slp-vectorize"]),
     ("personalize.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     ("animate.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),

@@ -1,0 +1,234 @@
+"""Paired evaluation on the device: SSIM, PSNR and the scale-shape-pose error of generated frames against ground truth, the
+paired protocol of the reference's evaluate.py (thirdparty/his_evaluators/.../metrics/metrics.py: SSIMMetric, PSNRMetric,
+ScaleShapePoseError) over csrc/eval.hip.  No float frame goes to the host: a frame leaves the device as four fp64 numbers
+(plus three for SSPE).  There is no CPU fallback; a missing kernel is an error.
+
+The arithmetic is stated in include/lwg.h (lwg_eval_pair_stats); tests/metrics_ref.py restates it in numpy.
+"""
+import math
+
+import numpy as np
+import torch
+
+from .. import _lib
+from ..ops import _chk
+
+HMR_SIZE = 224
+
+
+def _mode(mode):
+    if mode not in (0, 1, 2):
+        raise ValueError("mode must be 0 ([-1,1] as it is), 1 ([0,1] input) or 2 ([-1,1] through 8 bits), got %r" % (mode,))
+    return int(mode)
+
+
+@torch.no_grad()
+def pair_stats(pred, ref, mode=0, out=None):
+    """pred, ref (N,3,H,W) contiguous float32 CUDA tensors -> (N,4) float64 CUDA tensor [mssim, mse, ref_min, ref_max] per frame.
+    mode 0: values in [-1,1] as they are; 1: values in [0,1], mapped 2*x-1 as the reference's `preprocess` does; 2: values in
+    [-1,1] passed through the 8 bits the frame writer (cv_utils.save_cv2_img, truncating) and the evaluator's loader put between
+    generator and metric -- the quantisation only: JPEG loss is not modelled.
+    Only launches: no synchronisation.  `out`: an (N,4) float64 row block to write into (PairedEvaluator's device-side rows)."""
+    _chk(pred, ref)
+    if pred.dim() != 4 or pred.shape[1] != 3 or pred.shape != ref.shape:
+        raise ValueError("pair_stats takes two (N,3,H,W) tensors of one shape, got %s and %s" % (tuple(pred.shape), tuple(ref.shape)))
+    n, _, h, w = pred.shape
+    lib = _lib.load()
+    stats = out if out is not None else torch.empty((n, 4), device=pred.device, dtype=torch.float64)
+    if tuple(stats.shape) != (n, 4) or stats.dtype != torch.float64 or not stats.is_contiguous() or not stats.is_cuda:
+        raise ValueError("out must be a contiguous (N,4) float64 CUDA tensor")
+    nbytes = lib.lwg_eval_workspace_bytes(n, h, w)
+    ws = torch.empty(max(nbytes, 8), device=pred.device, dtype=torch.uint8)
+    _lib.check(lib.lwg_eval_pair_stats(_lib.ptr(pred), _lib.ptr(ref), n, h, w, _mode(mode), _lib.ptr(stats), _lib.ptr(ws), nbytes,
+                                       _lib.stream_ptr()))
+    return stats
+
+
+@torch.no_grad()
+def resize_bilinear(x, size):
+    """F.interpolate(x, size, mode='bilinear', align_corners=False) for a contiguous float32 CUDA (N,C,H,W) tensor."""
+    _chk(x)
+    if x.dim() != 4:
+        raise ValueError("resize_bilinear takes an (N,C,H,W) tensor, got %s" % (tuple(x.shape),))
+    ho, wo = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
+    n, c, h, w = x.shape
+    y = torch.empty((n, c, ho, wo), device=x.device, dtype=torch.float32)
+    _lib.check(_lib.load().lwg_resize_bilinear(_lib.ptr(x), n, c, h, w, ho, wo, _lib.ptr(y), _lib.stream_ptr()))
+    return y
+
+
+@torch.no_grad()
+def sspe_terms(a, b, out=None):
+    """a, b (N,85) contiguous float32 CUDA SMPL vectors -> (N,3) float64 CUDA tensor: |d[0]|, sum |d[75:85]|, sum |d[0:75]|
+    of d = a - b per frame (the reference's scale, shape and pose terms; its "pose" slice covers the three camera values again)."""
+    _chk(a, b)
+    if a.dim() != 2 or a.shape[1] != 85 or a.shape != b.shape:
+        raise ValueError("sspe_terms takes two (N,85) tensors, got %s and %s" % (tuple(a.shape), tuple(b.shape)))
+    n = a.shape[0]
+    terms = out if out is not None else torch.empty((n, 3), device=a.device, dtype=torch.float64)
+    if tuple(terms.shape) != (n, 3) or terms.dtype != torch.float64 or not terms.is_contiguous() or not terms.is_cuda:
+        raise ValueError("out must be a contiguous (N,3) float64 CUDA tensor")
+    _lib.check(_lib.load().lwg_eval_sspe_terms(_lib.ptr(a), _lib.ptr(b), n, _lib.ptr(terms), _lib.stream_ptr()))
+    return terms
+
+
+def psnr_from_stats(stats):
+    """Host, fp64: (N,4) rows of pair_stats -> (N,) PSNR as scikit-image 0.16.2's peak_signal_noise_ratio gives it for float
+    images without a data_range: 1 when the reference image has no negative value, else 2; +inf for identical images.
+    ValueError when the reference image leaves [-1,1] (scikit-image raises there)."""
+    stats = np.asarray(stats, np.float64).reshape(-1, 4)
+    out = np.empty(len(stats), np.float64)
+    for i, (_, mse, lo, hi) in enumerate(stats):
+        if lo < -1 or hi > 1:
+            raise ValueError("im_true has intensity values outside the range expected for its data type: [%g, %g] (frame %d)"
+                             % (lo, hi, i))
+        data_range = 1.0 if lo >= 0 else 2.0
+        out[i] = math.inf if mse == 0 else 10.0 * math.log10(data_range * data_range / mse)
+    return out
+
+
+def _as_batch(x):
+    """a list of (3,H,W) tensors (what the reference's calculate_score iterates over) is stacked; a tensor passes through"""
+    if not torch.is_tensor(x):
+        x = torch.stack(list(x))
+    return x
+
+
+class BaseMetric(object):
+    LOWER, HIGHER = "lower", "higher"
+
+
+class SSIMMetric(BaseMetric):
+    """metrics.py:450-507.  preds, gts: (N,3,H,W) images in [0,1] on the device (mode 1 maps them to [-1,1])."""
+
+    def calculate_score(self, preds, gts):
+        stats = pair_stats(_as_batch(preds), _as_batch(gts), mode=1)
+        return float(np.mean(stats[:, 0].cpu().numpy()))
+
+    def quality(self):
+        return self.HIGHER
+
+
+class PSNRMetric(BaseMetric):
+    """metrics.py:510-566.  preds, gts: (N,3,H,W) images in [0,1] on the device."""
+
+    def calculate_score(self, preds, gts):
+        stats = pair_stats(_as_batch(preds), _as_batch(gts), mode=1)
+        return float(np.mean(psnr_from_stats(stats.cpu().numpy())))
+
+    def quality(self):
+        return self.HIGHER
+
+
+class ScaleShapePoseError(BaseMetric):
+    """metrics.py:1048-1111 with the regressor on the device: `hmr` is a networks.hmr.HumanModelRecovery.  preds, gts:
+    (N,3,H,W) images in [0,1] as the reference's take them (`unit=False`: already in [-1,1], what the generator emits)."""
+
+    def __init__(self, hmr, unit=True):
+        if hmr is None or not hasattr(hmr, "regressor"):
+            raise ValueError("ScaleShapePoseError needs the HMR regressor (networks.hmr.HumanModelRecovery)")
+        self.hmr, self.unit = hmr, bool(unit)
+
+    @torch.no_grad()
+    def thetas(self, x):
+        """(N,3,H,W) -> (N,85): resize to 224x224 (F.interpolate, bilinear, align_corners=False), then the regressor"""
+        x = _as_batch(x)
+        _chk(x)
+        if self.unit:
+            x = x * 2 - 1             # metrics.py:1069-1071, two float32 roundings
+        if tuple(x.shape[-2:]) != (HMR_SIZE, HMR_SIZE):
+            x = resize_bilinear(x, (HMR_SIZE, HMR_SIZE))
+        return self.hmr(x)
+
+    def terms(self, preds, gts, out=None):
+        """device-side (N,3) float64 rows [scale, shape, pose]; only launches"""
+        return sspe_terms(self.thetas(preds), self.thetas(gts), out=out)
+
+    def calculate_score(self, preds, gts):
+        t = self.terms(preds, gts).cpu().numpy()
+        return float(t[:, 0].mean() + t[:, 1].mean() + t[:, 2].mean())
+
+    def quality(self):
+        return self.LOWER
+
+
+class PairedEvaluator(object):
+    """Scores a sequence batch by batch without leaving the device.
+
+        ev = PairedEvaluator(("ssim", "psnr"))            # frames in [-1,1] as the generator emits them (mode 0)
+        for t, preds in imitator.predict_batches(...):
+            ev.update(preds, ground_truth[t:t + len(preds)])
+        print(ev.result())
+
+    `update` only launches kernels: it writes the batch's rows into a device-side table (grown by doubling) and makes no
+    `.cpu()`, `.item()` or synchronisation call, so it can sit inside the imitation loop.  `result()` makes ONE device->host copy
+    and returns per-frame arrays and their means over frames.  The reference averages per-batch means instead
+    (BaseMetric.calculate_score over a loader); the two agree whenever the frame count is a multiple of the batch size.
+    mode: 0, 1 or 2 as in `pair_stats` (2 = "quantize": what an 8-bit writer would have stored).  SSPE is taken on the frames
+    as they are (mode 1: after 2*x-1); the quantiser of mode 2 applies to SSIM and PSNR only.
+    `hmr`: the regressor for "sspe" (networks.hmr.HumanModelRecovery); asking for "sspe" without it raises here."""
+
+    METRICS = ("ssim", "psnr", "sspe")
+    COLS = 7   # mssim, mse, ref_min, ref_max | scale, shape, pose
+
+    def __init__(self, metrics=("ssim", "psnr", "sspe"), hmr=None, mode=0):
+        metrics = tuple(metrics)
+        unknown = [m for m in metrics if m not in self.METRICS]
+        if unknown or not metrics:
+            raise ValueError("metrics must be among %s, got %s" % (self.METRICS, metrics))
+        self.metrics, self.mode = metrics, _mode(mode)
+        self._sspe = None
+        if "sspe" in metrics:
+            if hmr is None:
+                raise ValueError('"sspe" needs hmr=<networks.hmr.HumanModelRecovery>: the SMPL vectors come from the regressor')
+            self._sspe = ScaleShapePoseError(hmr, unit=self.mode == 1)
+        self._pixel = "ssim" in metrics or "psnr" in metrics
+        self._stats = self._terms = None
+        self._n = 0
+
+    def _rows(self, name, cols, n, device):
+        """a contiguous (n, cols) float64 block at the end of the named device-side table (grown by doubling, stream-ordered)"""
+        table = getattr(self, name)
+        if table is None or self._n + n > table.shape[0]:
+            grown = torch.empty((max(64, 2 * (self._n + n)), cols), device=device, dtype=torch.float64)
+            if table is not None:
+                grown[:self._n].copy_(table[:self._n])
+            setattr(self, name, grown)
+            table = grown
+        return table[self._n:self._n + n]
+
+    @torch.no_grad()
+    def update(self, pred, ref):
+        n = int(pred.shape[0])
+        if self._pixel:
+            pair_stats(pred, ref, self.mode, out=self._rows("_stats", 4, n, pred.device))
+        if self._sspe is not None:
+            self._sspe.terms(pred, ref, out=self._rows("_terms", 3, n, pred.device))
+        self._n += n
+
+    def __len__(self):
+        return self._n
+
+    def result(self):
+        """{"frames": n, "ssim": mean, "psnr": mean, "sspe": mean, "per_frame": {name: (n,) float64 array}}; the one host copy.
+        PSNR's ValueError for a reference image outside [-1,1] is raised here, when the numbers are read."""
+        n = self._n
+        cols = [t[:n] for t in (self._stats, self._terms) if t is not None]
+        if n == 0 or not cols:
+            return {"frames": 0, "per_frame": {}}
+        host = torch.cat(cols, dim=1).cpu().numpy()
+        out, per, k = {"frames": n}, {}, 0
+        if self._stats is not None:
+            if "ssim" in self.metrics:
+                per["ssim"] = host[:, 0].copy()
+            if "psnr" in self.metrics:
+                per["psnr"] = psnr_from_stats(host[:, 0:4])
+                per["mse"] = host[:, 1].copy()
+            k = 4
+        if self._terms is not None:
+            per["sspe_scale"], per["sspe_shape"], per["sspe_pose"] = (host[:, k + j].copy() for j in range(3))
+            per["sspe"] = host[:, k] + host[:, k + 1] + host[:, k + 2]
+        for name in self.metrics:
+            out[name] = float(np.mean(per[name]))
+        out["per_frame"] = per
+        return out

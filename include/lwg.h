@@ -226,6 +226,34 @@ LWG_API size_t lwg_jpeg_stream_bytes(int H, int W, int subsampling);
 LWG_API size_t lwg_jpeg_workspace_bytes(int N, int H, int W, int subsampling);
 LWG_API int lwg_jpeg_encode(const float *x, int N, int H, int W, int quality, int subsampling, uint8_t *out, size_t row_stride,
                             int32_t *lengths, void *workspace, size_t workspace_bytes, lwg_stream_t stream);
+/* ---- Paired evaluation of generated frames (csrc/eval.hip): the reference's SSIMMetric, PSNRMetric and ScaleShapePoseError
+ * (thirdparty/his_evaluators/.../metrics/metrics.py) without taking a float frame to the host.
+ * eval_pair_stats: pred, ref (N,3,H,W) fp32 NCHW -> stats (N,4) FP64 [mssim, mse, ref_min, ref_max] per frame.
+ *   mode 0: values as they are ([-1,1], what the generator emits);
+ *   mode 1: inputs in [0,1], mapped as the reference's `preprocess` does: fl32(fl32(2*x) - 1);
+ *   mode 2: [-1,1] through the 8 bits between writer and loader: u = clamp(trunc(fl32(fl32(fl32(x+1)/2)*255)), 0, 255)
+ *           (utils/cv_utils.py: save_cv2_img, normalize=True), v = fl32(fl32(fl32(u)/255)*2) - 1.  JPEG loss is not modelled.
+ *   mssim: scikit-image 0.16.2 structural_similarity(multichannel=True) on float32 images: 7x7 uniform window, data_range 2,
+ *     K1 0.01, K2 0.03 (C1 4e-4, C2 3.6e-3), cov_norm 49/48, S averaged over the (H-6)x(W-6) window positions inside the image per
+ *     channel, then over the three channels.  mse: mean of (pred-ref)^2 over all 3*H*W values.  ref_min / ref_max: over the
+ *     mapped ref (PSNR's data_range is 1 when ref_min >= 0, else 2; psnr = 10 log10(data_range^2 / mse), left to the caller).
+ *   Pixels are mapped in fp32; window sums, S and every mean are fp64.  Per-tile partials go to the workspace in a fixed layout
+ *   and are added in a fixed order: no atomics, bit-reproducible, and a frame's numbers do not depend on N or on its position
+ *   in the batch.  Stream-ordered, no host synchronisation.  lwg_eval_workspace_bytes needs no device (0 for sizes <= 0).
+ *   NULL, N / H / W <= 0, an unknown mode, stats or workspace not 8-byte aligned: LWG_ERR_INVALID_ARG; H < 7 or W < 7 (scikit-image
+ *   raises there) or N > 21845: LWG_ERR_UNSUPPORTED; a short workspace: LWG_ERR_WORKSPACE -- all before the first HIP call.
+ * resize_bilinear: F.interpolate(x, (Ho,Wo), mode='bilinear', align_corners=False), no antialiasing, x (N,C,H,W) -> y (N,C,Ho,Wo).
+ *   ATen's arithmetic per axis, float32: scale = (float)in / (float)out, src = max(fmaf(scale, dst+0.5f, -0.5f), 0) (the one fused
+ *   multiply-add: torch's binaries contract this expression; the lerps below round per step),
+ *   i0 = (int)src, i1 = min(i0+1, in-1), l = src - i0; value = (1-ly)*((1-lx)*a00 + lx*a01) + ly*((1-lx)*a10 + lx*a11).
+ *   (lwg_resize_flow above is the align_corners=True resize of the flow field.)
+ * eval_sspe_terms: pred_theta, ref_theta (N,85) fp32 -> terms (N,3) FP64 per frame: |d[0]|, sum |d[75:85]|, sum |d[0:75]| of
+ *   d = pred - ref taken in fp64 -- ssp_abs_err_score_func's scale, shape and "pose" terms, the last covering the camera again. */
+LWG_API size_t lwg_eval_workspace_bytes(int N, int H, int W);
+LWG_API int lwg_eval_pair_stats(const float *pred, const float *ref, int N, int H, int W, int mode, double *stats, void *workspace,
+                                size_t workspace_bytes, lwg_stream_t stream);
+LWG_API int lwg_resize_bilinear(const float *x, int N, int C, int H, int W, int Ho, int Wo, float *y, lwg_stream_t stream);
+LWG_API int lwg_eval_sspe_terms(const float *pred_theta, const float *ref_theta, int N, double *terms, lwg_stream_t stream);
 /* ---- Once-per-source glue of Imitator.personalize (models/imitator.py:82-155), so that `personalize` launches no
  * framework kernel.
  * morph: utils/util.py:73-89 -- erode (mode 0: pad with 1, count == ks*ks) / dilate (mode 1: pad with 0, count >= 1) of a
