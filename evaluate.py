@@ -1,16 +1,19 @@
 #!/usr/bin/env python
-"""Paired evaluation of motion imitation -- the counterpart of the reference's evaluate.py for its paired metrics (SSIM, PSNR
-and, with the HMR regressor, the scale-shape-pose error), computed on the device: no float frame goes to the host.
+"""Paired evaluation of motion imitation -- the counterpart of the reference's evaluate.py for its paired metrics (SSIM, PSNR,
+with the HMR regressor the scale-shape-pose error, with the AlexNet and LPIPS weights LPIPS), computed on the device: no float
+frame goes to the host.
 
     python evaluate.py --synthetic --num_frames 64 --output_dir OUT                 (no assets: default arithmetic vs exact fp32)
     python evaluate.py --src_path S.jpg --tgt_path DIR --load_path G.pth --output_dir OUT        (self-imitation, real assets)
     python evaluate.py ... --quantize                (score what an 8-bit writer would have stored)
     python evaluate.py ... --hmr_model H.pth         (adds SSPE)
+    python evaluate.py ... --lpips_alex A.pth --lpips_lin L.pth      (adds LPIPS v0.1 / alex: `lpips`, `lpips_max`; both or neither)
 
 Ground truth: `--against fp32` runs the sequence through the exact-fp32 generator first and scores the default arithmetic
 against it (the default under --synthetic, where no ground-truth pictures exist); `--against target` takes the frames of
 --tgt_path, loaded and resized as run_imitator.py loads them and uploaded per batch.  One JSON line goes to stdout and to
-<output_dir>/metrics.json.  LPIPS, IS/FID, re-id and face metrics need downloaded backbones and are not part of this.
+<output_dir>/metrics.json.  A.pth is torchvision's alexnet state_dict, L.pth the LPIPS v0.1 alex.pth; without the two flags the
+output carries no `lpips` key.  IS/FID, re-id and face metrics need downloaded backbones and are not part of this.
 """
 import json
 import os
@@ -72,16 +75,29 @@ def target_batch(paths, size):
     return torch.from_numpy(np.ascontiguousarray(np.stack(imgs), dtype=np.float32)).cuda()
 
 
+def load_lpips(opt):
+    """the LPIPS model of --lpips_alex / --lpips_lin, None without them; one flag alone is refused"""
+    if bool(opt.lpips_alex) != bool(opt.lpips_lin):
+        raise SystemExit("LPIPS needs both --lpips_alex (torchvision's AlexNet state_dict) and --lpips_lin (the LPIPS v0.1 "
+                         "alex.pth): only %s was given" % ('--lpips_alex' if opt.lpips_alex else '--lpips_lin'))
+    if not opt.lpips_alex:
+        return None
+    from impersonator_amd.networks.lpips import LPIPS
+    return LPIPS(torch.load(opt.lpips_alex, map_location='cpu'), torch.load(opt.lpips_lin, map_location='cpu'),
+                 max_batch=max(1, int(opt.batch_size)), image_size=opt.image_size)
+
+
 @torch.no_grad()
 def evaluate(opt):
+    lpips = load_lpips(opt)                                # a lone flag ends the run before anything is built
     imitator, personalize, tgt_smpls, tgt_paths = build(opt)
     gen = imitator.generator
     against = opt.against or ('target' if tgt_paths else 'fp32')
     if against == 'target' and not tgt_paths:
         raise SystemExit("--against target needs --tgt_path: there are no ground-truth pictures otherwise")
     hmr = imitator.hmr if hasattr(imitator.hmr, 'regressor') else None
-    names = ('ssim', 'psnr') + (('sspe',) if hmr is not None else ())
-    ev = PairedEvaluator(names, hmr=hmr, mode=2 if opt.quantize else 0)
+    names = ('ssim', 'psnr') + (('sspe',) if hmr is not None else ()) + (('lpips',) if lpips is not None else ())
+    ev = PairedEvaluator(names, hmr=hmr, mode=2 if opt.quantize else 0, lpips=lpips)
 
     truth = {}
     if against == 'fp32':
@@ -102,6 +118,8 @@ def evaluate(opt):
         out[k] = res[k]
     out['ssim_min'] = float(res['per_frame']['ssim'].min())
     out['psnr_min'] = float(res['per_frame']['psnr'].min())
+    if lpips is not None:
+        out['lpips_max'] = float(res['per_frame']['lpips'].max())
     return out
 
 

@@ -106,6 +106,14 @@ _PROTOS = {
     "lwg_hmr_pool_features": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "lwg_hmr_regress_workspace_bytes": (_sz, [_i]),
     "lwg_hmr_regress": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "lwg_lpips_create": (_i, [_c.POINTER(_vp), _i, _i, _i]),
+    "lwg_lpips_destroy": (None, [_vp]),
+    "lwg_lpips_weight_floats": (_sz, [_vp]),
+    "lwg_lpips_set_weights": (_i, [_vp, _vp, _sz]),
+    "lwg_lpips_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "lwg_lpips_conv": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "lwg_lpips_maxpool": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "lwg_lpips_layer_distance": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "lwg_conv2d_workspace_bytes": (_c.c_size_t, [_vp]),
     "lwg_conv2d_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _c.c_size_t, _vp]),
     "lwg_conv2d_backward_data": (_i, [_vp, _vp, _vp, _vp, _vp, _c.c_size_t, _vp]),

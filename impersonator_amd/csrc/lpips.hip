@@ -1,0 +1,593 @@
+// lpips.hip -- LPIPS v0.1 with the AlexNet backbone (the reference's PerceptualMetric: thirdparty/his_evaluators/.../metrics/lpips,
+// PNetLin('alex', version '0.1') in eval mode) for the paired evaluator: pred and ref frames in, one fp64 distance per frame out.
+//
+// The network is torchvision's alexnet().features[0:12]: conv 3->64 k11 s4 p2, ReLU, MaxPool(3,2), conv 64->192 k5 p2, ReLU,
+// MaxPool(3,2), conv 192->384 k3 p1, ReLU, conv 384->256 k3 p1, ReLU, conv 256->256 k3 p1, ReLU, with a tap after each ReLU.
+//
+//   lpips_conv_kernel: implicit GEMM on v_mfma_f32_32x32x2_f32 (bit-for-bit a k-ordered fmaf chain), exact fp32.  Workgroup = 64
+//   pixels x 64 output channels, four waves of one 32x32 tile, K = taps x Cin walked 32 at a time through a double-buffered LDS
+//   stage; the pixel dimension M = N*Ho*Wo is flattened across images and predicated at its tail.  Bias + ReLU in the epilogue.
+//   The first convolution reads the (n,3,H,W) NCHW frames of pred and ref directly (one batch of 2n images, so the weights are read
+//   once per layer); its prologue maps the pixel (the evaluator's three modes, as load_mapped of eval.hip) and applies LPIPS's
+//   scaling layer (x - shift) / scale, every step a separately rounded fp32 operation (the file is built without fp contraction).
+//   Padding applies AFTER the scaling: a padded tap contributes 0.
+//
+//   lpips_maxpool_kernel: F.max_pool2d(3, 2), floor mode, NHWC: rows and columns that no window covers are ignored.
+//
+//   lpips_distance_kernel: one tap's term of the distance, fused: per pixel s_i = sum_c x_i,c^2, n_i = sqrt(s_i) + 1e-10,
+//   d = sum_c w_c (x_0,c / n_0 - x_1,c / n_1)^2, then the sum of d over the pixels -- all in fp64 from the fp32 features.  16 lanes
+//   share a pixel: a lane adds its channels in ascending order, the 16 lanes are added by a fixed butterfly; a workgroup owns a
+//   chunk of 64 pixels and adds them by a fixed LDS tree; a frame's chunk sums are added in ascending order and divided by the
+//   pixel count (lpips_finalize_kernel, which also adds the five taps; the op-level entry makes the same additions inside the
+//   one kernel).  No atomics.
+//
+// The reduction order of every number depends on nothing but its own indices: a frame's features and distance are the same bits
+// at any batch size and any position in the batch, and (a - b)^2 == (b - a)^2 makes the distance the same bits with pred and ref
+// swapped.  One stream, no host synchronisation and no allocation in forward: capturable as a single chain of launches.
+#include <cstring>
+
+#include "common.h"
+
+namespace lwg {
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int BM = 64, BN = 64, BK = 32;
+constexpr int A_PITCH = BK + 1;   // odd pitch: the 32 rows a fragment read touches fall into 32 banks
+constexpr int B_PITCH = BN;
+
+// how a stored pixel becomes the value that is scored: the three modes of eval.hip's load_mapped, restated (that file's results
+// must not move, so nothing is shared with it); every step a separately rounded float32 operation
+//   0: as it is   1: [0,1] -> [-1,1], 2*x - 1   2: [-1,1] through the writer's 8 bits and the loader's way back
+__device__ __forceinline__ float map_pixel(float x, int mode)
+{
+    if (mode == 1) {
+        const float t = 2.f * x;
+        return t - 1.f;
+    }
+    if (mode == 2) {
+        const float a = x + 1.f;
+        const float b = a / 2.f;
+        const float c = b * 255.f;
+        float u = truncf(c);
+        u = u > 0.f ? u : 0.f;         // NaN -> 0 as well
+        u = u < 255.f ? u : 255.f;
+        const float d = u / 255.f;
+        const float e = d * 2.f;
+        return e - 1.f;
+    }
+    return x;
+}
+
+// LPIPS's ScalingLayer: (x - shift) / scale per colour channel, a subtraction and a true division
+__device__ __forceinline__ float scale_pixel(float v, int c)
+{
+    const float shift = c == 0 ? -.030f : (c == 1 ? -.088f : -.188f);
+    const float scale = c == 0 ? .458f : (c == 1 ? .448f : .450f);
+    const float d = v - shift;
+    return d / scale;
+}
+
+enum { IN_NHWC4 = 0, IN_NHWC = 1, IN_IMAGE = 2 };
+
+struct ConvP {
+    const float *x;          // NHWC (N,H,W,Cin); IN_IMAGE: images 0 .. split-1 as (split,3,H,W) NCHW
+    const float *x2;         // IN_IMAGE: images split .. N-1, NCHW
+    const float *w;          // (k*k*Cin, Cout): [tap][ci][co]
+    const float *bias;       // (Cout) or NULL
+    float *y;                // (N,Ho,Wo,Cout)
+    int N, split, H, W, Cin, Cout, ks, stride, pad, Ho, Wo, relu, mode;
+    long M;                  // N*Ho*Wo
+    int K;                   // ks*ks*Cin
+};
+
+// KIND: IN_NHWC4 -- Cin % 4 == 0, four consecutive reduction indices are one 16-byte load inside one tap; IN_NHWC -- any Cin;
+// IN_IMAGE -- Cin == 3, NCHW frames through map_pixel and scale_pixel
+template <int KIND>
+__global__ __launch_bounds__(256) void lpips_conv_kernel(const ConvP p)
+{
+    __shared__ __attribute__((aligned(16))) float sA[2][BM * A_PITCH];
+    __shared__ __attribute__((aligned(16))) float sB[2][BK * B_PITCH];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    const long m0 = (long)blockIdx.x * BM;
+    const int co0 = blockIdx.y * BN;
+
+    // A loader: rows (tid >> 3) and (tid >> 3) + 32, reduction indices (tid & 7) * 4 .. + 3 of the stage
+    const int a_col = (tid & 7) * 4;
+    int a_ih0[2], a_iw0[2];
+    const float *a_base[2];
+    bool a_ok[2];
+#pragma unroll
+    for (int v = 0; v < 2; ++v) {
+        const long m = m0 + (tid >> 3) + 32 * v;
+        a_ok[v] = m < p.M;
+        const long mm = a_ok[v] ? m : 0;
+        const int n = (int)(mm / ((long)p.Ho * p.Wo));
+        const int rem = (int)(mm - (long)n * p.Ho * p.Wo);
+        const int oh = rem / p.Wo, ow = rem - oh * p.Wo;
+        a_ih0[v] = oh * p.stride - p.pad;
+        a_iw0[v] = ow * p.stride - p.pad;
+        const size_t image = (size_t)p.H * p.W * p.Cin;
+        if (KIND == IN_IMAGE) a_base[v] = n < p.split ? p.x + (size_t)n * image : p.x2 + (size_t)(n - p.split) * image;
+        else a_base[v] = p.x + (size_t)n * image;
+    }
+    // B loader: reduction rows (tid >> 4) and (tid >> 4) + 16, output channels (tid & 15) * 4 .. + 3
+    const int b_col = (tid & 15) * 4;
+
+    float4 ra[2], rb[2];
+    auto gather1 = [&](int v, int kg) -> float {   // one input value; 0 outside the image, past K or past M
+        if (!a_ok[v] || kg >= p.K) return 0.f;
+        const int tap = kg / p.Cin, c = kg - tap * p.Cin;
+        const int kh = tap / p.ks, kw = tap - kh * p.ks;
+        const int ih = a_ih0[v] + kh, iw = a_iw0[v] + kw;
+        if ((unsigned)ih >= (unsigned)p.H || (unsigned)iw >= (unsigned)p.W) return 0.f;
+        if (KIND == IN_IMAGE) return scale_pixel(map_pixel(a_base[v][((size_t)c * p.H + ih) * p.W + iw], p.mode), c);
+        return a_base[v][((size_t)ih * p.W + iw) * p.Cin + c];
+    };
+    auto load = [&](int k0) {
+        const int kg = k0 + a_col;
+#pragma unroll
+        for (int v = 0; v < 2; ++v) {
+            if (KIND == IN_NHWC4) {
+                ra[v] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (a_ok[v] && kg < p.K) {
+                    const int tap = kg / p.Cin, c = kg - tap * p.Cin;
+                    const int kh = tap / p.ks, kw = tap - kh * p.ks;
+                    const int ih = a_ih0[v] + kh, iw = a_iw0[v] + kw;
+                    if ((unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W)
+                        ra[v] = *reinterpret_cast<const float4 *>(a_base[v] + ((size_t)ih * p.W + iw) * p.Cin + c);
+                }
+            } else {
+                ra[v] = make_float4(gather1(v, kg), gather1(v, kg + 1), gather1(v, kg + 2), gather1(v, kg + 3));
+            }
+        }
+#pragma unroll
+        for (int v = 0; v < 2; ++v) {
+            const int kr = k0 + (tid >> 4) + 16 * v;
+            rb[v] = kr < p.K ? *reinterpret_cast<const float4 *>(p.w + (size_t)kr * p.Cout + co0 + b_col)
+                             : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    };
+    auto store = [&](int buf) {
+#pragma unroll
+        for (int v = 0; v < 2; ++v) {
+            float *d = &sA[buf][((tid >> 3) + 32 * v) * A_PITCH + a_col];
+            d[0] = ra[v].x;
+            d[1] = ra[v].y;
+            d[2] = ra[v].z;
+            d[3] = ra[v].w;
+            *reinterpret_cast<float4 *>(&sB[buf][((tid >> 4) + 16 * v) * B_PITCH + b_col]) = rb[v];
+        }
+    };
+
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+
+    int buf = 0;
+    load(0);
+    store(0);
+    __syncthreads();
+    for (int k0 = 0; k0 < p.K; k0 += BK) {
+        const bool more = k0 + BK < p.K;
+        if (more) load(k0 + BK);
+        // A: lane -> pixel row (lane & 31), k = lane >> 5;  B: lane -> output channel (lane & 31), k = lane >> 5
+        const float *ar = &sA[buf][(wm * 32 + (lane & 31)) * A_PITCH + (lane >> 5)];
+        const float *br = &sB[buf][(lane >> 5) * B_PITCH + wn * 32 + (lane & 31)];
+#pragma unroll
+        for (int kk = 0; kk < BK / 2; ++kk)
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ar[2 * kk], br[2 * kk * B_PITCH], acc, 0, 0, 0);
+        if (more) store(buf ^ 1);
+        __syncthreads();
+        buf ^= 1;
+    }
+
+    // C/D layout: col = lane & 31 -> output channel, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5) -> pixel
+    const int co = co0 + wn * 32 + (lane & 31);
+    const float bias = p.bias ? p.bias[co] : 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const long m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        if (m >= p.M) continue;
+        float v = acc[r];
+        if (p.bias) v += bias;
+        if (p.relu) v = fmaxf(v, 0.f);
+        p.y[(size_t)m * p.Cout + co] = v;
+    }
+}
+
+// max_pool2d(kernel 3, stride 2), floor mode, no padding, NHWC, C % 4 == 0: every window lies inside the input
+__global__ __launch_bounds__(256) void lpips_maxpool_kernel(const float *__restrict__ x, int H, int W, int C4, int Ho, int Wo,
+                                                           long total, float *__restrict__ y)
+{
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;   // over N*Ho*Wo*C4
+    if (i >= total) return;
+    const int c4 = (int)(i % C4);
+    long px = i / C4;
+    const int ow = (int)(px % Wo);
+    px /= Wo;
+    const int oh = (int)(px % Ho);
+    const long n = px / Ho;
+    const float4 *xs = reinterpret_cast<const float4 *>(x);
+    float4 m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+#pragma unroll
+    for (int kh = 0; kh < 3; ++kh) {
+#pragma unroll
+        for (int kw = 0; kw < 3; ++kw) {
+            const float4 v = xs[((n * H + (oh * 2 + kh)) * W + (ow * 2 + kw)) * C4 + c4];
+            m.x = fmaxf(m.x, v.x);
+            m.y = fmaxf(m.y, v.y);
+            m.z = fmaxf(m.z, v.z);
+            m.w = fmaxf(m.w, v.w);
+        }
+    }
+    reinterpret_cast<float4 *>(y)[i] = m;
+}
+
+constexpr int kDistThreads = 1024, kDistLanes = 16, kChunk = kDistThreads / kDistLanes;   // 64 pixels per chunk
+constexpr int kTaps = 5;
+
+// the sum over the 16 lanes that share a pixel; every lane ends with the same bits (a + b == b + a)
+__device__ __forceinline__ double group_sum(double v)
+{
+#pragma unroll
+    for (int off = kDistLanes / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// f0, f1 (n,P,C) NHWC features of the two halves, C4 = C / 4, w (C).  A frame's pixels are cut into chunks of 64; a workgroup
+// computes a chunk's sum of d (one pixel per 16-lane group, then the LDS tree).  The grid is n * wgs_per_frame workgroups:
+//   partial != NULL (wgs_per_frame == chunks): partial[frame][chunk] = the chunk's sum; lpips_finalize_kernel adds them;
+//   partial == NULL (wgs_per_frame == 1): the frame's workgroup walks its chunks, adds their sums in ascending order -- the same
+//   additions in the same order as the finalize kernel makes -- and writes out[frame * out_stride] = the mean of d.
+__global__ __launch_bounds__(kDistThreads) void lpips_distance_kernel(const float *__restrict__ f0, const float *__restrict__ f1, int P,
+                                                                     int C4, const float *__restrict__ w, int wgs_per_frame,
+                                                                     double *__restrict__ partial, double *__restrict__ out,
+                                                                     int out_stride)
+{
+    __shared__ double part[kChunk];
+    const int frame = blockIdx.x / wgs_per_frame, first = blockIdx.x % wgs_per_frame;
+    const int tid = threadIdx.x, g = tid / kDistLanes, sub = tid % kDistLanes;
+    const int chunks = (P + kChunk - 1) / kChunk;
+    const float4 *a = reinterpret_cast<const float4 *>(f0) + (size_t)frame * P * C4;
+    const float4 *b = reinterpret_cast<const float4 *>(f1) + (size_t)frame * P * C4;
+    const float4 *w4 = reinterpret_cast<const float4 *>(w);
+    double total = 0.0;
+    for (int chunk = first; chunk < chunks; chunk += wgs_per_frame) {
+        const int px = chunk * kChunk + g;
+        double d = 0.0;
+        if (px < P) {
+            const float4 *pa = a + (size_t)px * C4, *pb = b + (size_t)px * C4;
+            double s0 = 0.0, s1 = 0.0;
+            for (int c = sub; c < C4; c += kDistLanes) {
+                const float4 u = pa[c], v = pb[c];
+                s0 += (double)u.x * (double)u.x;
+                s0 += (double)u.y * (double)u.y;
+                s0 += (double)u.z * (double)u.z;
+                s0 += (double)u.w * (double)u.w;
+                s1 += (double)v.x * (double)v.x;
+                s1 += (double)v.y * (double)v.y;
+                s1 += (double)v.z * (double)v.z;
+                s1 += (double)v.w * (double)v.w;
+            }
+            const double n0 = sqrt(group_sum(s0)) + 1e-10, n1 = sqrt(group_sum(s1)) + 1e-10;
+            for (int c = sub; c < C4; c += kDistLanes) {
+                const float4 u = pa[c], v = pb[c], q = w4[c];
+                const double tx = (double)u.x / n0 - (double)v.x / n1;
+                const double ty = (double)u.y / n0 - (double)v.y / n1;
+                const double tz = (double)u.z / n0 - (double)v.z / n1;
+                const double tw = (double)u.w / n0 - (double)v.w / n1;
+                d += (double)q.x * (tx * tx);
+                d += (double)q.y * (ty * ty);
+                d += (double)q.z * (tz * tz);
+                d += (double)q.w * (tw * tw);
+            }
+            d = group_sum(d);
+        }
+        if (sub == 0) part[g] = d;
+        __syncthreads();
+#pragma unroll
+        for (int s = kChunk / 2; s > 0; s >>= 1) {
+            if (tid < s) part[tid] += part[tid + s];
+            __syncthreads();
+        }
+        if (tid == 0) {
+            if (partial) partial[(size_t)frame * chunks + chunk] = part[0];
+            else total += part[0];
+        }
+        __syncthreads();               // part is written again in the next round
+    }
+    if (!partial && tid == 0) out[(size_t)frame * out_stride] = total / (double)P;
+}
+
+struct TapPlan {
+    int P[kTaps], chunks[kTaps];
+    long off[kTaps];                   // where the tap's (n, chunks) block of partial sums starts
+};
+
+// one lane per frame: each tap's chunk sums added in ascending order and divided by its pixel count, then the frame's LPIPS:
+// its five taps added in tap order
+__global__ __launch_bounds__(64) void lpips_finalize_kernel(const double *__restrict__ partial, const TapPlan tp, int n,
+                                                           double *__restrict__ taps, double *__restrict__ dist)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    double s = 0.0;
+    for (int t = 0; t < kTaps; ++t) {
+        const double *q = partial + tp.off[t] + (size_t)i * tp.chunks[t];
+        double total = 0.0;
+        for (int c = 0; c < tp.chunks[t]; ++c) total += q[c];
+        const double v = total / (double)tp.P[t];
+        taps[(size_t)i * kTaps + t] = v;
+        s = t == 0 ? v : s + v;
+    }
+    dist[i] = s;
+}
+
+// ------------------------------------------------------------------------------------------------ host side
+struct Layer {
+    int Cin, Cout, ks, stride, pad, pool;   // pool: MaxPool(3,2) between this layer's tap and the next convolution
+};
+constexpr Layer kLayers[kTaps] = {{3, 64, 11, 4, 2, 1}, {64, 192, 5, 1, 2, 1}, {192, 384, 3, 1, 1, 0}, {384, 256, 3, 1, 1, 0},
+                                  {256, 256, 3, 1, 1, 0}};
+constexpr int kMinSize = 31;   // 31 -> 7 -> 3 -> 1: the smallest size at which relu5 still has a pixel
+
+bool conv_geometry_ok(int k, int stride, int pad)
+{
+    return (k == 11 && stride == 4 && pad == 2) || (k == 5 && stride == 1 && pad == 2) || (k == 3 && stride == 1 && pad == 1);
+}
+
+inline int conv_out(int in, const Layer &l) { return (in + 2 * l.pad - l.ks) / l.stride + 1; }
+inline int pool_out(int in) { return (in - 3) / 2 + 1; }
+
+int launch_conv(ConvP p, int kind, hipStream_t st)
+{
+    p.Ho = (p.H + 2 * p.pad - p.ks) / p.stride + 1;
+    p.Wo = (p.W + 2 * p.pad - p.ks) / p.stride + 1;
+    p.M = (long)p.N * p.Ho * p.Wo;
+    p.K = p.ks * p.ks * p.Cin;
+    const dim3 grid((unsigned)ceil_div(p.M, BM), (unsigned)(p.Cout / BN));
+    if (kind == IN_IMAGE) lpips_conv_kernel<IN_IMAGE><<<grid, 256, 0, st>>>(p);
+    else if (kind == IN_NHWC4) lpips_conv_kernel<IN_NHWC4><<<grid, 256, 0, st>>>(p);
+    else lpips_conv_kernel<IN_NHWC><<<grid, 256, 0, st>>>(p);
+    LWG_LAUNCH_CHECK("lpips_conv_kernel");
+    return LWG_OK;
+}
+
+int launch_maxpool(const float *x, int N, int H, int W, int C, float *y, hipStream_t st)
+{
+    const int Ho = pool_out(H), Wo = pool_out(W);
+    const long total = (long)N * Ho * Wo * (C / 4);
+    lpips_maxpool_kernel<<<ceil_div(total, 256), 256, 0, st>>>(x, H, W, C / 4, Ho, Wo, total, y);
+    LWG_LAUNCH_CHECK("lpips_maxpool_kernel");
+    return LWG_OK;
+}
+
+inline int chunks_of(long P) { return ceil_div(P, kChunk); }
+
+// partial != NULL: one workgroup per chunk, the chunk sums go to partial (n, chunks); NULL: one workgroup per frame, out (n)
+int launch_distance(const float *f0, const float *f1, int n, int P, int C, const float *w, double *partial, double *out, hipStream_t st)
+{
+    const int per_frame = partial ? chunks_of(P) : 1;
+    lpips_distance_kernel<<<(unsigned)((long)n * per_frame), kDistThreads, 0, st>>>(f0, f1, P, C / 4, w, per_frame, partial, out, 1);
+    LWG_LAUNCH_CHECK("lpips_distance_kernel");
+    return LWG_OK;
+}
+
+inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+}  // namespace
+}  // namespace lwg
+
+using namespace lwg;
+
+struct lwg_lpips {
+    int max_pairs = 0, max_h = 0, max_w = 0;
+    long w_off[kTaps] = {0}, b_off[kTaps] = {0}, lin_off[kTaps] = {0};   // blob offsets in floats
+    size_t blob_floats = 0;
+    float *blob = nullptr;
+    float *feat[kTaps] = {nullptr};    // the five taps of the 2 * max_pairs images, NHWC
+    float *pooled[2] = {nullptr};      // what the second and third convolutions read
+    double *taps = nullptr;            // (max_pairs, 5) when the caller wants the distances only
+    double *partial = nullptr;         // the chunk sums of the five taps
+    bool ready = false;
+};
+
+namespace {
+
+// The blob layout -- what impersonator_amd/networks/lpips.py::pack_weights writes, in this order:
+//   per conv: w (k,k,Cin,Cout) [kh][kw][ci][co] | bias (Cout);  then the five lin vectors (64, 192, 384, 256, 256)
+void build_plan(lwg_lpips *h)
+{
+    long off = 0;
+    for (int l = 0; l < kTaps; ++l) {
+        h->w_off[l] = off;
+        off += (long)kLayers[l].ks * kLayers[l].ks * kLayers[l].Cin * kLayers[l].Cout;
+        h->b_off[l] = off;
+        off += kLayers[l].Cout;
+    }
+    for (int l = 0; l < kTaps; ++l) {
+        h->lin_off[l] = off;
+        off += kLayers[l].Cout;
+    }
+    h->blob_floats = (size_t)off;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lwg_lpips_create(lwg_lpips **out, int max_pairs, int max_h, int max_w)
+{
+    LWG_REQUIRE(out != nullptr, "lwg_lpips_create: NULL output handle");
+    *out = nullptr;
+    LWG_REQUIRE(max_pairs >= 1 && max_pairs <= 4096, "lwg_lpips_create: max_pairs %d outside 1..4096", max_pairs);
+    LWG_REQUIRE(max_h >= kMinSize && max_w >= kMinSize && max_h <= 8192 && max_w <= 8192,
+                "lwg_lpips_create: max_h x max_w = %d x %d outside %d..8192", max_h, max_w, kMinSize);
+    lwg_lpips *h = new lwg_lpips();
+    h->max_pairs = max_pairs;
+    h->max_h = max_h;
+    h->max_w = max_w;
+    build_plan(h);
+    auto alloc = [&](float **p, size_t n) { return hipMalloc(reinterpret_cast<void **>(p), n * sizeof(float)); };
+    hipError_t e = alloc(&h->blob, h->blob_floats);
+    int H = max_h, W = max_w, npool = 0;
+    long chunks = 0;
+    for (int l = 0; l < kTaps && e == hipSuccess; ++l) {
+        H = conv_out(H, kLayers[l]);
+        W = conv_out(W, kLayers[l]);
+        chunks += chunks_of((long)H * W);
+        e = alloc(&h->feat[l], (size_t)2 * max_pairs * H * W * kLayers[l].Cout);
+        if (kLayers[l].pool && e == hipSuccess) {
+            H = pool_out(H);
+            W = pool_out(W);
+            e = alloc(&h->pooled[npool++], (size_t)2 * max_pairs * H * W * kLayers[l].Cout);
+        }
+    }
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&h->taps), (size_t)max_pairs * kTaps * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&h->partial), (size_t)max_pairs * chunks * sizeof(double));
+    if (e != hipSuccess) {
+        lwg_lpips_destroy(h);
+        LWG_FAIL(LWG_ERR_HIP, "lwg_lpips_create: hipMalloc failed: %s", hipGetErrorString(e));
+    }
+    *out = h;
+    return LWG_OK;
+}
+
+void lwg_lpips_destroy(lwg_lpips *h)
+{
+    if (!h) return;
+    auto fr = [](void *p) { if (p) (void)hipFree(p); };
+    fr(h->blob);
+    for (int l = 0; l < kTaps; ++l) fr(h->feat[l]);
+    fr(h->pooled[0]);
+    fr(h->pooled[1]);
+    fr(h->taps);
+    fr(h->partial);
+    delete h;
+}
+
+size_t lwg_lpips_weight_floats(const lwg_lpips *h) { return h ? h->blob_floats : 0; }
+
+int lwg_lpips_set_weights(lwg_lpips *h, const float *blob_host, size_t n_floats)
+{
+    LWG_REQUIRE(h != nullptr, "lwg_lpips_set_weights: NULL handle");
+    LWG_REQUIRE(blob_host != nullptr, "lwg_lpips_set_weights: NULL blob");
+    LWG_REQUIRE(n_floats == h->blob_floats, "lwg_lpips_set_weights: blob of %zu floats, this network takes %zu", n_floats, h->blob_floats);
+    h->ready = false;
+    // synchronous: the caller's host buffer may go away after the call, and no forward may overlap the replacement
+    LWG_HIP(hipDeviceSynchronize());
+    LWG_HIP(hipMemcpy(h->blob, blob_host, n_floats * sizeof(float), hipMemcpyHostToDevice));
+    h->ready = true;
+    return LWG_OK;
+}
+
+int lwg_lpips_forward(lwg_lpips *h, const float *pred, const float *ref, int n, int H, int W, int mode, double *dist, double *taps,
+                      lwg_stream_t stream)
+{
+    LWG_REQUIRE(h != nullptr, "lwg_lpips_forward: NULL handle");
+    LWG_REQUIRE(pred != nullptr && ref != nullptr && dist != nullptr, "lwg_lpips_forward: NULL pred, ref or dist");
+    LWG_REQUIRE(n >= 1 && H >= 1 && W >= 1, "lwg_lpips_forward: sizes must be positive (n=%d H=%d W=%d)", n, H, W);
+    LWG_REQUIRE(mode >= 0 && mode <= 2, "lwg_lpips_forward: mode %d is none of 0 (as is), 1 ([0,1] input), 2 (8-bit round trip)", mode);
+    LWG_REQUIRE(((reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(ref)) & 3) == 0, "lwg_lpips_forward: images must be 4-byte aligned");
+    LWG_REQUIRE(((reinterpret_cast<uintptr_t>(dist) | reinterpret_cast<uintptr_t>(taps)) & 7) == 0, "lwg_lpips_forward: dist and taps must be 8-byte aligned (fp64)");
+    if (H < kMinSize || W < kMinSize)
+        LWG_FAIL(LWG_ERR_UNSUPPORTED, "lwg_lpips_forward: %d x %d is below %d x %d, the smallest size at which relu5 has a pixel", H, W, kMinSize, kMinSize);
+    if (n > h->max_pairs) LWG_FAIL(LWG_ERR_STATE, "lwg_lpips_forward: n = %d above max_pairs = %d", n, h->max_pairs);
+    if (H > h->max_h || W > h->max_w)
+        LWG_FAIL(LWG_ERR_STATE, "lwg_lpips_forward: %d x %d above max_h x max_w = %d x %d", H, W, h->max_h, h->max_w);
+    if (!h->ready) LWG_FAIL(LWG_ERR_STATE, "lwg_lpips_forward: no weights set");
+    hipStream_t st = as_stream(stream);
+    const float *src = nullptr;
+    int ch = H, cw = W, npool = 0;
+    TapPlan tp;
+    long off = 0;
+    for (int l = 0; l < kTaps; ++l) {
+        const Layer &L = kLayers[l];
+        ConvP p;
+        memset(&p, 0, sizeof(p));
+        p.x = l == 0 ? pred : src;
+        p.x2 = l == 0 ? ref : nullptr;
+        p.w = h->blob + h->w_off[l];
+        p.bias = h->blob + h->b_off[l];
+        p.y = h->feat[l];
+        p.N = 2 * n; p.split = n; p.H = ch; p.W = cw; p.Cin = L.Cin; p.Cout = L.Cout; p.ks = L.ks; p.stride = L.stride; p.pad = L.pad;
+        p.relu = 1; p.mode = mode;
+        int rc = launch_conv(p, l == 0 ? IN_IMAGE : IN_NHWC4, st);
+        if (rc != LWG_OK) return rc;
+        ch = conv_out(ch, L);
+        cw = conv_out(cw, L);
+        const int P = ch * cw;
+        tp.P[l] = P;
+        tp.chunks[l] = chunks_of(P);
+        tp.off[l] = off;
+        rc = launch_distance(h->feat[l], h->feat[l] + (size_t)n * P * L.Cout, n, P, L.Cout, h->blob + h->lin_off[l], h->partial + off,
+                             nullptr, st);
+        if (rc != LWG_OK) return rc;
+        off += (long)n * tp.chunks[l];
+        src = h->feat[l];
+        if (L.pool) {
+            rc = launch_maxpool(h->feat[l], 2 * n, ch, cw, L.Cout, h->pooled[npool], st);
+            if (rc != LWG_OK) return rc;
+            src = h->pooled[npool++];
+            ch = pool_out(ch);
+            cw = pool_out(cw);
+        }
+    }
+    lpips_finalize_kernel<<<ceil_div(n, 64), 64, 0, st>>>(h->partial, tp, n, taps ? taps : h->taps, dist);
+    LWG_LAUNCH_CHECK("lpips_finalize_kernel");
+    return LWG_OK;
+}
+
+int lwg_lpips_conv(const float *x, int N, int H, int W, int Cin, const float *w, const float *bias, int Cout, int k, int stride,
+                   int pad, int relu, int input_mode, float *y, lwg_stream_t stream)
+{
+    LWG_REQUIRE(x != nullptr && w != nullptr && y != nullptr, "lwg_lpips_conv: NULL x, w or y");
+    LWG_REQUIRE(N >= 1 && H >= 1 && W >= 1 && Cin >= 1 && Cout >= 1, "lwg_lpips_conv: non-positive size");
+    LWG_REQUIRE(relu == 0 || relu == 1, "lwg_lpips_conv: relu = %d is neither 0 nor 1", relu);
+    LWG_REQUIRE(input_mode <= 2, "lwg_lpips_conv: input_mode %d is none of < 0 (NHWC), 0, 1, 2 (NCHW frames in that pixel mode)", input_mode);
+    LWG_REQUIRE(input_mode < 0 || Cin == 3, "lwg_lpips_conv: the frame prologue takes 3 channels, got Cin = %d", Cin);
+    // 16-byte accesses: the weight rows always, the input when it is NHWC with Cin a multiple of 4
+    LWG_REQUIRE(aligned16(w), "lwg_lpips_conv: w is not 16-byte aligned");
+    LWG_REQUIRE((reinterpret_cast<uintptr_t>(x) & 3) == 0 && (reinterpret_cast<uintptr_t>(y) & 3) == 0 &&
+                (reinterpret_cast<uintptr_t>(bias) & 3) == 0, "lwg_lpips_conv: x / y / bias are not 4-byte aligned");
+    LWG_REQUIRE(input_mode >= 0 || Cin % 4 != 0 || aligned16(x), "lwg_lpips_conv: x is not 16-byte aligned");
+    if (!conv_geometry_ok(k, stride, pad))
+        LWG_FAIL(LWG_ERR_UNSUPPORTED, "lwg_lpips_conv: (k, stride, pad) = (%d, %d, %d) is none of (11,4,2) (5,1,2) (3,1,1)", k, stride, pad);
+    if (Cout % lwg::BN != 0) LWG_FAIL(LWG_ERR_UNSUPPORTED, "lwg_lpips_conv: Cout = %d is no multiple of %d", Cout, lwg::BN);
+    if ((long)N * H * W * (long)(Cin > Cout ? Cin : Cout) >= (1L << 40)) LWG_FAIL(LWG_ERR_UNSUPPORTED, "lwg_lpips_conv: tensor too large");
+    const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
+    LWG_REQUIRE(H + 2 * pad >= k && W + 2 * pad >= k && Ho >= 1 && Wo >= 1, "lwg_lpips_conv: empty output");
+    if ((long)k * k * Cin > 0x7fffffffL || ((long)N * Ho * Wo + lwg::BM - 1) / lwg::BM > 0x7fffffffL)
+        LWG_FAIL(LWG_ERR_UNSUPPORTED, "lwg_lpips_conv: tensor too large");
+    ConvP p;
+    memset(&p, 0, sizeof(p));
+    p.x = x; p.x2 = x; p.w = w; p.bias = bias; p.y = y;
+    p.N = N; p.split = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.ks = k; p.stride = stride; p.pad = pad;
+    p.relu = relu; p.mode = input_mode < 0 ? 0 : input_mode;
+    return launch_conv(p, input_mode >= 0 ? IN_IMAGE : (Cin % 4 == 0 ? IN_NHWC4 : IN_NHWC), as_stream(stream));
+}
+
+int lwg_lpips_maxpool(const float *x, int N, int H, int W, int C, float *y, lwg_stream_t stream)
+{
+    LWG_REQUIRE(x != nullptr && y != nullptr, "lwg_lpips_maxpool: NULL x or y");
+    LWG_REQUIRE(N >= 1 && H >= 3 && W >= 3 && C >= 1, "lwg_lpips_maxpool: needs N, C >= 1 and H, W >= 3");
+    if (C % 4 != 0) LWG_FAIL(LWG_ERR_UNSUPPORTED, "lwg_lpips_maxpool: C = %d is no multiple of 4", C);
+    LWG_REQUIRE(aligned16(x) && aligned16(y), "lwg_lpips_maxpool: x / y are not 16-byte aligned");
+    if ((long)N * pool_out(H) * pool_out(W) * (C / 4) > 256L * 0x7fffffffL) LWG_FAIL(LWG_ERR_UNSUPPORTED, "lwg_lpips_maxpool: tensor too large");
+    return launch_maxpool(x, N, H, W, C, y, as_stream(stream));
+}
+
+int lwg_lpips_layer_distance(const float *f0, const float *f1, int n, int P, int C, const float *w, double *out, lwg_stream_t stream)
+{
+    LWG_REQUIRE(f0 != nullptr && f1 != nullptr && w != nullptr && out != nullptr, "lwg_lpips_layer_distance: NULL f0, f1, w or out");
+    LWG_REQUIRE(n >= 1 && P >= 1 && C >= 1, "lwg_lpips_layer_distance: sizes must be positive (n=%d P=%d C=%d)", n, P, C);
+    if (C % 4 != 0) LWG_FAIL(LWG_ERR_UNSUPPORTED, "lwg_lpips_layer_distance: C = %d is no multiple of 4", C);
+    LWG_REQUIRE(aligned16(f0) && aligned16(f1) && aligned16(w), "lwg_lpips_layer_distance: f0 / f1 / w are not 16-byte aligned");
+    LWG_REQUIRE((reinterpret_cast<uintptr_t>(out) & 7) == 0, "lwg_lpips_layer_distance: out must be 8-byte aligned (fp64)");
+    return launch_distance(f0, f1, n, P, C, w, nullptr, out, as_stream(stream));
+}
+
+}  // extern "C"

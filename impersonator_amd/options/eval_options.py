@@ -1,5 +1,6 @@
-"""Command-line flags of evaluate.py (the paired metrics of the reference's evaluate.py: SSIM, PSNR, SSPE).  Every flag of
-TestOptions stays as it is; `--hmr_model`, when it names a checkpoint of the HMR regressor, adds SSPE."""
+"""Command-line flags of evaluate.py (the paired metrics of the reference's evaluate.py: SSIM, PSNR, SSPE, LPIPS).  Every flag of
+TestOptions stays as it is; `--hmr_model`, when it names a checkpoint of the HMR regressor, adds SSPE; `--lpips_alex` and
+`--lpips_lin` together add LPIPS."""
 from .test_options import TestOptions
 
 
@@ -12,3 +13,7 @@ class EvalOptions(TestOptions):
                             "without --tgt_path), 'target' = the frames of --tgt_path (self-imitation)")
         p.add_argument('--quantize', action='store_true', default=False,
                        help='score what an 8-bit writer would have stored (truncating uint8 round trip; JPEG loss is not modelled)')
+        p.add_argument('--lpips_alex', type=str, default='',
+                       help="torchvision's AlexNet state_dict (features.{0,3,6,8,10}.weight / .bias); with --lpips_lin adds LPIPS")
+        p.add_argument('--lpips_lin', type=str, default='',
+                       help="the LPIPS v0.1 linear layers (alex.pth: lin{0..4}.model.1.weight); with --lpips_alex adds LPIPS")

@@ -1,7 +1,7 @@
-"""Paired evaluation on the device: SSIM, PSNR and the scale-shape-pose error of generated frames against ground truth, the
-paired protocol of the reference's evaluate.py (thirdparty/his_evaluators/.../metrics/metrics.py: SSIMMetric, PSNRMetric,
-ScaleShapePoseError) over csrc/eval.hip.  No float frame goes to the host: a frame leaves the device as four fp64 numbers
-(plus three for SSPE).  There is no CPU fallback; a missing kernel is an error.
+"""Paired evaluation on the device: SSIM, PSNR, LPIPS and the scale-shape-pose error of generated frames against ground truth,
+the paired protocol of the reference's evaluate.py (thirdparty/his_evaluators/.../metrics/metrics.py: SSIMMetric, PSNRMetric,
+PerceptualMetric, ScaleShapePoseError) over csrc/eval.hip and csrc/lpips.hip.  No float frame goes to the host: a frame leaves
+the device as four fp64 numbers (plus three for SSPE, plus one for LPIPS).  There is no CPU fallback; a missing kernel is an error.
 
 The arithmetic is stated in include/lwg.h (lwg_eval_pair_stats); tests/metrics_ref.py restates it in numpy.
 """
@@ -152,6 +152,22 @@ class ScaleShapePoseError(BaseMetric):
         return self.LOWER
 
 
+class PerceptualMetric(BaseMetric):
+    """metrics.py:569-640 with the network on the device: `lpips` is a networks.lpips.LPIPS (AlexNet, v0.1).  preds, gts:
+    (N,3,H,W) images in [0,1] on the device (mode 1 maps them to [-1,1], as the reference's `preprocess` does)."""
+
+    def __init__(self, lpips):
+        if lpips is None or not callable(lpips) or not hasattr(lpips, "max_batch"):
+            raise ValueError("PerceptualMetric needs the LPIPS model (networks.lpips.LPIPS)")
+        self.lpips = lpips
+
+    def calculate_score(self, preds, gts):
+        return float(np.mean(self.lpips(_as_batch(preds), _as_batch(gts), mode=1).cpu().numpy()))
+
+    def quality(self):
+        return self.LOWER
+
+
 class PairedEvaluator(object):
     """Scores a sequence batch by batch without leaving the device.
 
@@ -163,15 +179,18 @@ class PairedEvaluator(object):
     `update` only launches kernels: it writes the batch's rows into a device-side table (grown by doubling) and makes no
     `.cpu()`, `.item()` or synchronisation call, so it can sit inside the imitation loop.  `result()` makes ONE device->host copy
     and returns per-frame arrays and their means over frames.  The reference averages per-batch means instead
-    (BaseMetric.calculate_score over a loader); the two agree whenever the frame count is a multiple of the batch size.
+    (BaseMetric.calculate_score over a loader, PerceptualMetric.calculate_score in batches of 32 -- LPIPS included); the two
+    agree whenever the frame count is a multiple of the batch size.
     mode: 0, 1 or 2 as in `pair_stats` (2 = "quantize": what an 8-bit writer would have stored).  SSPE is taken on the frames
-    as they are (mode 1: after 2*x-1); the quantiser of mode 2 applies to SSIM and PSNR only.
-    `hmr`: the regressor for "sspe" (networks.hmr.HumanModelRecovery); asking for "sspe" without it raises here."""
+    as they are (mode 1: after 2*x-1); the quantiser of mode 2 applies to SSIM, PSNR and LPIPS.  All three modes apply to both
+    images.
+    `hmr`: the regressor for "sspe" (networks.hmr.HumanModelRecovery); asking for "sspe" without it raises here.
+    `lpips`: the model for "lpips" (networks.lpips.LPIPS); asking for "lpips" without it raises here, in the same way."""
 
-    METRICS = ("ssim", "psnr", "sspe")
-    COLS = 7   # mssim, mse, ref_min, ref_max | scale, shape, pose
+    METRICS = ("ssim", "psnr", "sspe", "lpips")
+    COLS = 8   # mssim, mse, ref_min, ref_max | scale, shape, pose | lpips
 
-    def __init__(self, metrics=("ssim", "psnr", "sspe"), hmr=None, mode=0):
+    def __init__(self, metrics=("ssim", "psnr", "sspe"), hmr=None, mode=0, lpips=None):
         metrics = tuple(metrics)
         unknown = [m for m in metrics if m not in self.METRICS]
         if unknown or not metrics:
@@ -182,8 +201,13 @@ class PairedEvaluator(object):
             if hmr is None:
                 raise ValueError('"sspe" needs hmr=<networks.hmr.HumanModelRecovery>: the SMPL vectors come from the regressor')
             self._sspe = ScaleShapePoseError(hmr, unit=self.mode == 1)
+        self._lpips = None
+        if "lpips" in metrics:
+            if lpips is None:
+                raise ValueError('"lpips" needs lpips=<networks.lpips.LPIPS>: the distance comes from the AlexNet model')
+            self._lpips = PerceptualMetric(lpips).lpips
         self._pixel = "ssim" in metrics or "psnr" in metrics
-        self._stats = self._terms = None
+        self._stats = self._terms = self._dists = None
         self._n = 0
 
     def _rows(self, name, cols, n, device):
@@ -204,16 +228,19 @@ class PairedEvaluator(object):
             pair_stats(pred, ref, self.mode, out=self._rows("_stats", 4, n, pred.device))
         if self._sspe is not None:
             self._sspe.terms(pred, ref, out=self._rows("_terms", 3, n, pred.device))
+        if self._lpips is not None:
+            self._lpips(pred, ref, self.mode, out=self._rows("_dists", 1, n, pred.device).view(n))
         self._n += n
 
     def __len__(self):
         return self._n
 
     def result(self):
-        """{"frames": n, "ssim": mean, "psnr": mean, "sspe": mean, "per_frame": {name: (n,) float64 array}}; the one host copy.
+        """{"frames": n, "ssim": mean, "psnr": mean, "sspe": mean, "lpips": mean, "per_frame": {name: (n,) float64 array}}; the one
+        host copy.
         PSNR's ValueError for a reference image outside [-1,1] is raised here, when the numbers are read."""
         n = self._n
-        cols = [t[:n] for t in (self._stats, self._terms) if t is not None]
+        cols = [t[:n] for t in (self._stats, self._terms, self._dists) if t is not None]
         if n == 0 or not cols:
             return {"frames": 0, "per_frame": {}}
         host = torch.cat(cols, dim=1).cpu().numpy()
@@ -228,6 +255,9 @@ class PairedEvaluator(object):
         if self._terms is not None:
             per["sspe_scale"], per["sspe_shape"], per["sspe_pose"] = (host[:, k + j].copy() for j in range(3))
             per["sspe"] = host[:, k] + host[:, k + 1] + host[:, k + 2]
+            k += 3
+        if self._dists is not None:
+            per["lpips"] = host[:, k].copy()
         for name in self.metrics:
             out[name] = float(np.mean(per[name]))
         out["per_frame"] = per

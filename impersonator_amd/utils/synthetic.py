@@ -254,3 +254,18 @@ def hmr_state_dict(seed, num_blocks=(3, 4, 6, 3)):
     linear("regressor.fc_blocks.fc2", 1024, 1024)
     linear("regressor.fc_blocks.fc3", 85, 1024, gain=0.1)
     return out
+
+
+def lpips_state_dicts(seed):
+    """Seeded weights of LPIPS v0.1 / alex -> (alex, lin): `alex` with torchvision's alexnet keys (features.{0,3,6,8,10}.weight /
+    .bias), `lin` with the keys of the LPIPS alex.pth (lin{0..4}.model.1.weight, (1,C,1,1)).  numpy RandomState, one draw per
+    tensor: He-normal conv weights, small biases, and NON-NEGATIVE lin weights, as the trained ones are.  The 2.47 M conv weights
+    are regenerated from the seed wherever they are needed; they are never stored."""
+    rs = np.random.RandomState(seed)
+    alex, lin = {}, {}
+    for i, cout, cin, k in ((0, 64, 3, 11), (3, 192, 64, 5), (6, 384, 192, 3), (8, 256, 384, 3), (10, 256, 256, 3)):
+        alex["features.%d.weight" % i] = (rs.standard_normal((cout, cin, k, k)) * math.sqrt(2.0 / (cin * k * k))).astype(np.float32)
+        alex["features.%d.bias" % i] = (rs.standard_normal(cout) * 0.05).astype(np.float32)
+    for j, c in enumerate((64, 192, 384, 256, 256)):
+        lin["lin%d.model.1.weight" % j] = (rs.uniform(0.0, 2.0, (1, c, 1, 1)) / c).astype(np.float32)
+    return alex, lin

@@ -473,6 +473,49 @@ LWG_API int lwg_hmr_regress(const float *features, int N, const float *mean_thet
                             const float *fc2_w, const float *fc2_b, const float *fc3_w, const float *fc3_b, float *theta_out,
                             void *workspace, size_t workspace_bytes, lwg_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * LPIPS (csrc/lpips.hip): the reference's PerceptualMetric -- PerceptualLoss(model='net-lin', net='alex'), version 0.1
+ * (thirdparty/his_evaluators/.../metrics/lpips: PNetLin.forward) in eval mode -- for the paired evaluator: pred and ref frames in,
+ * one FP64 distance per frame out, no float frame taken to the host.
+ * The network is torchvision's alexnet().features[0:12]: conv 3->64 k11 s4 p2 | ReLU | MaxPool(3,2) | conv 64->192 k5 p2 | ReLU |
+ * MaxPool(3,2) | conv 192->384 k3 p1 | ReLU | conv 384->256 k3 p1 | ReLU | conv 256->256 k3 p1 | ReLU, tapped after each ReLU.
+ * Exact fp32 convolutions (v_mfma_f32_32x32x2_f32, K = (tap, ci) ascending), NHWC activations, pred and ref as ONE batch of 2n
+ * images; per tap and frame, in fp64 from the fp32 features: s_i = sum_c x_i,c^2, n_i = sqrt(s_i) + 1e-10,
+ * d = sum_c w_c (x_0,c/n_0 - x_1,c/n_1)^2, the mean of d over the pixels; the frame's distance is the sum of its five taps in tap
+ * order.  Fixed reduction orders, no atomics: a frame's numbers are the same bits at any batch size, at any position in the
+ * batch, and with pred and ref swapped.  One stream, no host synchronisation, no allocation after create: a forward can be
+ * captured in a HIP graph as one chain of launches.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct lwg_lpips lwg_lpips;
+/* Scratch for 2 * max_pairs images of up to max_h x max_w (both >= 31) is allocated here. */
+LWG_API int lwg_lpips_create(lwg_lpips **out, int max_pairs, int max_h, int max_w);
+LWG_API void lwg_lpips_destroy(lwg_lpips *h);
+/* The weights as ONE packed fp32 blob (HOST memory) of lwg_lpips_weight_floats() floats
+ * (impersonator_amd/networks/lpips.py::pack_weights is the one writer).  Order:
+ *   per conv: w (k,k,Cin,Cout) [kh][kw][ci][co] | bias (Cout);  then the five lin vectors (64, 192, 384, 256, 256).
+ * Synchronises the device (the blob is replaced under no running forward). */
+LWG_API size_t lwg_lpips_weight_floats(const lwg_lpips *h);
+LWG_API int lwg_lpips_set_weights(lwg_lpips *h, const float *blob_host, size_t n_floats);
+/* pred, ref (n,3,H,W) fp32 NCHW -> dist (n) FP64, taps (n,5) FP64 or NULL.  mode: the pixel modes 0, 1, 2 of lwg_eval_pair_stats,
+ * applied to both images in front of LPIPS's scaling layer (x - shift) / scale, shift = (-.030, -.088, -.188), scale = (.458, .448,
+ * .450), every step a separately rounded fp32 operation; zero padding applies after the scaling.
+ * H or W < 31 (31 -> 7 -> 3 -> 1: the smallest size at which relu5 still has a pixel): LWG_ERR_UNSUPPORTED; n > max_pairs, H > max_h,
+ * W > max_w or no weights set: LWG_ERR_STATE; a mode outside 0..2: LWG_ERR_INVALID_ARG. */
+LWG_API int lwg_lpips_forward(lwg_lpips *h, const float *pred, const float *ref, int n, int H, int W, int mode, double *dist,
+                              double *taps, lwg_stream_t stream);
+/* Op-level entry points (what lwg_lpips_forward is made of; the tests call them directly).  Every argument is checked before the
+ * first HIP call.
+ * conv: w (k,k,Cin,Cout) [kh][kw][ci][co], bias (Cout) or NULL -> y (N,Ho,Wo,Cout) NHWC; (k,stride,pad) one of (11,4,2) (5,1,2)
+ *   (3,1,1), Cout a multiple of 64 (else LWG_ERR_UNSUPPORTED); relu 0 / 1.  input_mode < 0: x is (N,H,W,Cin) NHWC as it is;
+ *   0..2: x is (N,3,H,W) NCHW and the pixel mode + scaling prologue applies.  w 16-byte aligned, and x when NHWC with Cin % 4 == 0.
+ * maxpool: F.max_pool2d(kernel 3, stride 2), floor mode, no padding: (N,H,W,C) -> (N,(H-3)/2+1,(W-3)/2+1,C); C % 4 == 0, H, W >= 3.
+ * layer_distance: f0, f1 (n,P,C) NHWC feature blocks, w (C) -> out (n) FP64, one tap's term as stated above; C % 4 == 0. */
+LWG_API int lwg_lpips_conv(const float *x, int N, int H, int W, int Cin, const float *w, const float *bias, int Cout, int k,
+                           int stride, int pad, int relu, int input_mode, float *y, lwg_stream_t stream);
+LWG_API int lwg_lpips_maxpool(const float *x, int N, int H, int W, int C, float *y, lwg_stream_t stream);
+LWG_API int lwg_lpips_layer_distance(const float *f0, const float *f1, int n, int P, int C, const float *w, double *out,
+                                     lwg_stream_t stream);
+
 /* ---- training, first slice: the PatchGAN discriminator update ---------------------------------
  * Replaces PatchDiscriminator.forward (networks/discriminator.py:8-57, norm_type='instance', use_sigmoid=False) and,
  * for the discriminator, ImpersonatorTrainer._optimize_D + loss.backward() + torch.optim.Adam.step()
