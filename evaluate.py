@@ -8,12 +8,18 @@ frame goes to the host.
     python evaluate.py ... --quantize                (score what an 8-bit writer would have stored)
     python evaluate.py ... --hmr_model H.pth         (adds SSPE)
     python evaluate.py ... --lpips_alex A.pth --lpips_lin L.pth      (adds LPIPS v0.1 / alex: `lpips`, `lpips_max`; both or neither)
+    python evaluate.py ... --inception I.pth         (adds FID and Inception Score: `fid`, `is`, `is_std`)
 
 Ground truth: `--against fp32` runs the sequence through the exact-fp32 generator first and scores the default arithmetic
 against it (the default under --synthetic, where no ground-truth pictures exist); `--against target` takes the frames of
 --tgt_path, loaded and resized as run_imitator.py loads them and uploaded per batch.  One JSON line goes to stdout and to
 <output_dir>/metrics.json.  A.pth is torchvision's alexnet state_dict, L.pth the LPIPS v0.1 alex.pth; without the two flags the
-output carries no `lpips` key.  IS/FID, re-id and face metrics need downloaded backbones and are not part of this.
+output carries no `lpips` key.  I.pth is torchvision's inception_v3 state_dict (or a torch.save of
+utils.synthetic.inception_state_dict(0)): the predictions and the ground-truth frames the paired metrics score are also scored as
+two sets -- FID between them, the Inception Score of the predictions per batch of 32 (the reference's FIDMetric and
+InceptionScoreMetric, the softmax over the 2048 pool features included) -- on the host in fp64 from features computed on the device;
+the 2048 x 2048 matrix square root takes a few seconds.  Without the flag the output carries none of the three keys.  Re-id and
+face metrics need downloaded backbones and are not part of this.
 """
 import json
 import os
@@ -28,7 +34,7 @@ sys.path.insert(0, ROOT)
 from impersonator_amd import demo  # noqa: E402
 from impersonator_amd.options.eval_options import EvalOptions  # noqa: E402
 from impersonator_amd.utils import cv_utils, util  # noqa: E402
-from impersonator_amd.utils.metrics import PairedEvaluator  # noqa: E402
+from impersonator_amd.utils.metrics import PairedEvaluator, SetEvaluator  # noqa: E402
 from run_imitator import _smpl_of, _target_smpls, scan_tgt_paths  # noqa: E402
 
 
@@ -87,9 +93,18 @@ def load_lpips(opt):
                  max_batch=max(1, int(opt.batch_size)), image_size=opt.image_size)
 
 
+def load_inception(opt):
+    """the InceptionV3 model of --inception, None without it"""
+    if not opt.inception:
+        return None
+    from impersonator_amd.networks.inception import InceptionV3
+    return InceptionV3(torch.load(opt.inception, map_location='cpu'), max_batch=max(1, int(opt.batch_size)), image_size=opt.image_size)
+
+
 @torch.no_grad()
 def evaluate(opt):
     lpips = load_lpips(opt)                                # a lone flag ends the run before anything is built
+    inception = load_inception(opt)
     imitator, personalize, tgt_smpls, tgt_paths = build(opt)
     gen = imitator.generator
     against = opt.against or ('target' if tgt_paths else 'fp32')
@@ -98,6 +113,7 @@ def evaluate(opt):
     hmr = imitator.hmr if hasattr(imitator.hmr, 'regressor') else None
     names = ('ssim', 'psnr') + (('sspe',) if hmr is not None else ()) + (('lpips',) if lpips is not None else ())
     ev = PairedEvaluator(names, hmr=hmr, mode=2 if opt.quantize else 0, lpips=lpips)
+    sets = SetEvaluator(inception, mode=2 if opt.quantize else 0) if inception is not None else None
 
     truth = {}
     if against == 'fp32':
@@ -111,6 +127,8 @@ def evaluate(opt):
     for t, preds in imitator.predict_batches(batches_of(imitator, tgt_smpls, opt), opt.cam_strategy):
         ref = truth[t] if against == 'fp32' else target_batch(tgt_paths[t:t + preds.shape[0]], opt.image_size)
         ev.update(preds, ref)
+        if sets is not None:
+            sets.update(preds, ref)
     res = ev.result()                                      # the one device->host copy
     out = {'frames': res['frames'], 'ground_truth': 'fp32 generator' if against == 'fp32' else 'target frames',
            'precision': gen.precision, 'quantize': bool(opt.quantize), 'image_size': opt.image_size}
@@ -120,6 +138,9 @@ def evaluate(opt):
     out['psnr_min'] = float(res['per_frame']['psnr'].min())
     if lpips is not None:
         out['lpips_max'] = float(res['per_frame']['lpips'].max())
+    if sets is not None:
+        scores = sets.result()                             # one device->host copy per feature table, then fp64 on the host
+        out['fid'], out['is'], out['is_std'] = scores['fid'], scores['is'], scores['is_std']
     return out
 
 

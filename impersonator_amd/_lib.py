@@ -114,6 +114,15 @@ _PROTOS = {
     "lwg_lpips_conv": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "lwg_lpips_maxpool": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "lwg_lpips_layer_distance": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "lwg_inception_create": (_i, [_c.POINTER(_vp), _i, _i, _i]),
+    "lwg_inception_destroy": (None, [_vp]),
+    "lwg_inception_weight_floats": (_sz, []),
+    "lwg_inception_set_weights": (_i, [_vp, _vp, _sz]),
+    "lwg_inception_forward": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "lwg_inception_conv": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp]),
+    "lwg_inception_maxpool": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
+    "lwg_inception_avgpool": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "lwg_inception_global_pool": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "lwg_conv2d_workspace_bytes": (_c.c_size_t, [_vp]),
     "lwg_conv2d_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _c.c_size_t, _vp]),
     "lwg_conv2d_backward_data": (_i, [_vp, _vp, _vp, _vp, _vp, _c.c_size_t, _vp]),

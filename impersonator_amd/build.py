@@ -42,6 +42,8 @@ SOURCES = [
     ("hmr.hip", ["-fno-slp-vectorize"]),
     # the pixel modes and the scaling layer in front of the first convolution round per step, as eval.hip's do
     ("lpips.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
+    # the pixel modes and the resize in front of the first convolution round per step, as eval.hip's do
+    ("inception.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     ("train.hip", []),
     ("scatter.hip", []),
 ]

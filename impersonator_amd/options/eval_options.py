@@ -1,6 +1,6 @@
-"""Command-line flags of evaluate.py (the paired metrics of the reference's evaluate.py: SSIM, PSNR, SSPE, LPIPS).  Every flag of
+"""Command-line flags of evaluate.py (the metrics of the reference's evaluate.py: SSIM, PSNR, SSPE, LPIPS, FID, IS).  Every flag of
 TestOptions stays as it is; `--hmr_model`, when it names a checkpoint of the HMR regressor, adds SSPE; `--lpips_alex` and
-`--lpips_lin` together add LPIPS."""
+`--lpips_lin` together add LPIPS; `--inception` adds FID and the Inception Score."""
 from .test_options import TestOptions
 
 
@@ -17,3 +17,6 @@ class EvalOptions(TestOptions):
                        help="torchvision's AlexNet state_dict (features.{0,3,6,8,10}.weight / .bias); with --lpips_lin adds LPIPS")
         p.add_argument('--lpips_lin', type=str, default='',
                        help="the LPIPS v0.1 linear layers (alex.pth: lin{0..4}.model.1.weight); with --lpips_alex adds LPIPS")
+        p.add_argument('--inception', type=str, default='',
+                       help="torchvision's inception_v3 state_dict (<name>.conv.weight, <name>.bn.*; AuxLogits and fc are ignored); "
+                            "adds fid, is and is_std over the same predictions and ground-truth frames")

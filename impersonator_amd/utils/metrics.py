@@ -4,6 +4,10 @@ PerceptualMetric, ScaleShapePoseError) over csrc/eval.hip and csrc/lpips.hip.  N
 the device as four fp64 numbers (plus three for SSPE, plus one for LPIPS).  There is no CPU fallback; a missing kernel is an error.
 
 The arithmetic is stated in include/lwg.h (lwg_eval_pair_stats); tests/metrics_ref.py restates it in numpy.
+
+Set metrics, for the protocols without a ground-truth frame: FID and Inception Score (FIDMetric, InceptionScoreMetric of the same
+file) from InceptionV3 features computed on the device (csrc/inception.hip) -- SetEvaluator, FIDMetric, InceptionScoreMetric and
+the host-side fp64 functions frechet_distance, fid_from_features, inception_score at the end of this module.
 """
 import math
 
@@ -261,4 +265,149 @@ class PairedEvaluator(object):
         for name in self.metrics:
             out[name] = float(np.mean(per[name]))
         out["per_frame"] = per
+        return out
+
+
+# ------------------------------------------------------------------------------------------------ set metrics: FID and IS
+INCEPTION_SIZE = 299
+
+
+def frechet_distance(mu1, s1, mu2, s2, eps=1e-6):
+    """Host, fp64 (metrics.py:309-361, calculate_frechet_distance): |mu1 - mu2|^2 + Tr(s1) + Tr(s2) - 2 Tr(sqrtm(s1 s2)).
+    A square root that is not finite is taken again with eps added to both diagonals; a complex one (a singular product gives
+    one) must have a diagonal that is real to 1e-3 -- ValueError otherwise -- and its real part is used."""
+    from scipy import linalg
+    mu1, mu2 = np.atleast_1d(np.asarray(mu1, np.float64)), np.atleast_1d(np.asarray(mu2, np.float64))
+    s1, s2 = np.atleast_2d(np.asarray(s1, np.float64)), np.atleast_2d(np.asarray(s2, np.float64))
+    if mu1.shape != mu2.shape or s1.shape != s2.shape:
+        raise ValueError("the two sets have different feature dimensions: %s / %s and %s / %s" % (mu1.shape, s1.shape, mu2.shape, s2.shape))
+    diff = mu1 - mu2
+    covmean, _ = linalg.sqrtm(s1.dot(s2), disp=False)
+    if not np.isfinite(covmean).all():
+        offset = np.eye(s1.shape[0]) * eps
+        covmean = linalg.sqrtm((s1 + offset).dot(s2 + offset))
+    if np.iscomplexobj(covmean):
+        if not np.allclose(np.diagonal(covmean).imag, 0, atol=1e-3):
+            raise ValueError("Imaginary component {}".format(np.max(np.abs(covmean.imag))))
+        covmean = covmean.real
+    return float(diff.dot(diff) + np.trace(s1) + np.trace(s2) - 2 * np.trace(covmean))
+
+
+def fid_from_features(a, b):
+    """Host, fp64 (metrics.py:363-379, fid_score_func): a (Na,d), b (Nb,d) feature sets -> their Frechet distance from np.mean
+    and np.cov(rowvar=False); 0 when either set is empty."""
+    if len(a) == 0 or len(b) == 0:
+        return 0
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return frechet_distance(np.mean(a, axis=0), np.cov(a, rowvar=False), np.mean(b, axis=0), np.cov(b, rowvar=False))
+
+
+def inception_score(features, batch_size=32):
+    """Host, fp64 (metrics.py:381-395, 671-698): per batch of `batch_size` rows (the last may be short), the softmax over the
+    features AS THEY ARE -- the reference's network ends at the 2048 pool features, not at 1000 logits, and that is reproduced --
+    then exp(mean_i sum_j p_ij (log p_ij - log mean_i p_ij)); -> (mean, std) over the batches.  (0, 0) for an empty set."""
+    features = np.asarray(features, np.float64)
+    if len(features) == 0:
+        return 0.0, 0.0
+    scores = []
+    for s in range(0, len(features), int(batch_size)):
+        z = features[s:s + int(batch_size)]
+        z = z - z.max(axis=1, keepdims=True)
+        e = np.exp(z)
+        p = e / e.sum(axis=1, keepdims=True)
+        kl = p * (np.log(p) - np.log(np.expand_dims(np.mean(p, 0), 0)))
+        scores.append(np.exp(np.mean(np.sum(kl, 1))))
+    return float(np.mean(scores)), float(np.std(scores))
+
+
+def _inception(inception, who):
+    if inception is None or not callable(inception) or not hasattr(inception, "max_batch"):
+        raise ValueError("%s needs the InceptionV3 model (networks.inception.InceptionV3)" % who)
+    return inception
+
+
+class FIDMetric(BaseMetric):
+    """metrics.py:704-781 with the network on the device: `inception` is a networks.inception.InceptionV3.  preds, gts:
+    (N,3,H,W) images in [0,1] on the device (mode 1 maps them to [-1,1], then the resize to 299 x 299)."""
+
+    def __init__(self, inception):
+        self.inception = _inception(inception, "FIDMetric")
+
+    def features(self, x):
+        return self.inception(_as_batch(x), mode=1, resize=INCEPTION_SIZE).cpu().numpy().astype(np.float64)
+
+    def calculate_score(self, preds, gts):
+        return fid_from_features(self.features(preds), self.features(gts))
+
+    def quality(self):
+        return self.LOWER
+
+
+class InceptionScoreMetric(BaseMetric):
+    """metrics.py:634-701 with the network on the device.  preds: (N,3,H,W) images in [0,1] on the device -> (mean, std)."""
+
+    def __init__(self, inception):
+        self.inception = _inception(inception, "InceptionScoreMetric")
+
+    def calculate_score(self, preds, batch_size=32):
+        feats = self.inception(_as_batch(preds), mode=1, resize=INCEPTION_SIZE).cpu().numpy()
+        return inception_score(feats, batch_size)
+
+    def quality(self):
+        return self.HIGHER
+
+
+class SetEvaluator(object):
+    """FID and Inception Score of a sequence, batch by batch, without leaving the device: the unpaired protocols of the reference
+    (cross-imitation, appearance transfer, novel views) have no ground-truth frame, only two sets.
+
+        ev = SetEvaluator(inception)                       # frames in [-1,1] as the generator emits them (mode 0)
+        for t, preds in imitator.predict_batches(...):
+            ev.update(preds, real_frames[t:t + len(preds)])       # or ev.update(preds): Inception Score only
+        print(ev.result())
+
+    `update` only launches kernels: the (n,2048) features go to the end of a device-side table (grown by doubling) and no
+    `.cpu()`, `.item()` or synchronisation call is made.  `result()` makes ONE device->host copy per table and computes the
+    metrics on the host in fp64: {"frames", "is", "is_std"} and, when refs were given, {"fid", "is_ref"}.
+    mode: 0, 1 or 2 as in `pair_stats`, applied to preds and refs alike before the resize to 299 x 299."""
+
+    def __init__(self, inception, mode=0):
+        self.inception, self.mode = _inception(inception, "SetEvaluator"), _mode(mode)
+        self._pred = self._ref = None
+        self._n = {"_pred": 0, "_ref": 0}
+
+    def _rows(self, name, n, device):
+        table, used = getattr(self, name), self._n[name]
+        if table is None or used + n > table.shape[0]:
+            grown = torch.empty((max(64, 2 * (used + n)), 2048), device=device, dtype=torch.float32)
+            if table is not None:
+                grown[:used].copy_(table[:used])
+            setattr(self, name, grown)
+            table = grown
+        self._n[name] = used + n
+        return table[used:used + n]
+
+    @torch.no_grad()
+    def update(self, pred, ref=None):
+        self.inception(pred, mode=self.mode, out=self._rows("_pred", int(pred.shape[0]), pred.device), resize=INCEPTION_SIZE)
+        if ref is not None:
+            self.inception(ref, mode=self.mode, out=self._rows("_ref", int(ref.shape[0]), ref.device), resize=INCEPTION_SIZE)
+
+    def __len__(self):
+        return self._n["_pred"]
+
+    def features(self):
+        """-> (pred, ref) float64 host arrays (ref None when no refs were given); one device->host copy per table"""
+        host = lambda name: None if getattr(self, name) is None else getattr(self, name)[:self._n[name]].cpu().numpy().astype(np.float64)
+        return host("_pred"), host("_ref")
+
+    def result(self, batch_size=32):
+        pred, ref = self.features()
+        if pred is None or len(pred) == 0:
+            return {"frames": 0}
+        mean, std = inception_score(pred, batch_size)
+        out = {"frames": len(pred), "is": mean, "is_std": std}
+        if ref is not None:
+            out["fid"] = float(fid_from_features(pred, ref))
+            out["is_ref"] = inception_score(ref, batch_size)[0]
         return out

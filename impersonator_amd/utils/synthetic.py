@@ -269,3 +269,22 @@ def lpips_state_dicts(seed):
     for j, c in enumerate((64, 192, 384, 256, 256)):
         lin["lin%d.model.1.weight" % j] = (rs.uniform(0.0, 2.0, (1, c, 1, 1)) / c).astype(np.float32)
     return alex, lin
+
+
+def inception_state_dict(seed):
+    """Seeded weights of torchvision's inception_v3 as the evaluator runs it (the 94 `<name>.conv.weight` / `<name>.bn.*` groups of
+    networks/inception.py::CONVS, in that order; AuxLogits and fc are never run and are not drawn).  numpy RandomState, one draw
+    per tensor: He-normal conv weights and the NON-TRIVIAL BatchNorm statistics of `hmr_state_dict` -- gamma ~ U(0.5,1.5),
+    beta ~ N(0,0.1), running_mean ~ N(0,0.2), running_var ~ U(0.5,2) -- because an identity BatchNorm would let a wrong fold pass.
+    The 21.8 M weights are regenerated from the seed wherever they are needed; they are never stored."""
+    from ..networks.inception import CONVS
+    rs = np.random.RandomState(seed)
+    out = {}
+    for name, cin, cout, (kh, kw), _, _ in CONVS:
+        out[name + ".conv.weight"] = (rs.standard_normal((cout, cin, kh, kw)) * math.sqrt(2.0 / (cin * kh * kw))).astype(np.float32)
+        out[name + ".bn.weight"] = rs.uniform(0.5, 1.5, cout).astype(np.float32)
+        out[name + ".bn.bias"] = (rs.standard_normal(cout) * 0.1).astype(np.float32)
+        out[name + ".bn.running_mean"] = (rs.standard_normal(cout) * 0.2).astype(np.float32)
+        out[name + ".bn.running_var"] = rs.uniform(0.5, 2.0, cout).astype(np.float32)
+        out[name + ".bn.num_batches_tracked"] = np.zeros((), np.int64)
+    return out

@@ -516,6 +516,59 @@ LWG_API int lwg_lpips_maxpool(const float *x, int N, int H, int W, int C, float 
 LWG_API int lwg_lpips_layer_distance(const float *f0, const float *f1, int n, int P, int C, const float *w, double *out,
                                      lwg_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * InceptionV3 features (csrc/inception.hip) for the set metrics FID and Inception Score: the reference's
+ * InceptionV3(output_blocks=[3], resize_input=False, normalize_input=False) (thirdparty/his_evaluators/.../metrics/metrics.py:16-158,
+ * registered at 197-205) -- torchvision's inception_v3 in eval mode cut at the final average pool, `transform_input`, AuxLogits and
+ * fc never run -- behind the preprocessing of FIDMetric / InceptionScoreMetric (metrics.py:645-669, 715-740): `out *= 2; out -= 1`,
+ * then F.interpolate(out, (299,299), 'bilinear', align_corners=False).  Frames in, 2048 fp32 features per frame out.
+ * 94 x (Conv2d(bias=False) + BatchNorm2d(eps=1e-3) + ReLU) as exact fp32 convolutions (v_mfma_f32_32x32x2_f32, K = (kh, kw, ci)
+ * ascending) over NHWC activations with the BatchNorm folded into a per-channel fmaf(acc, scale, shift); MaxPool(3,2) floor mode;
+ * avg_pool2d(3,1,1) dividing by 9 everywhere; the global mean added in ascending pixel order in fp64 and rounded once.  The branches
+ * of a Mixed block write their channel slices of the block's output themselves.  Fixed reduction orders, no atomics: a frame's
+ * features are the same bits at any batch size and at any position in the batch.  One stream, no host synchronisation, no
+ * allocation after create: a forward can be captured in a HIP graph as one chain of launches.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct lwg_inception lwg_inception;
+/* Scratch for max_images frames of up to max_h x max_w -- taken as they are or resized to 299 x 299 -- is allocated here. */
+LWG_API int lwg_inception_create(lwg_inception **out, int max_images, int max_h, int max_w);
+LWG_API void lwg_inception_destroy(lwg_inception *h);
+/* The weights as ONE packed fp32 blob (HOST memory) of lwg_inception_weight_floats() floats
+ * (impersonator_amd/networks/inception.py::pack_weights is the one writer).  Per convolution, in torchvision's definition order
+ * (Conv2d_1a_3x3 ... Mixed_7c.branch_pool): w (kh,kw,Cin,Cout) [kh][kw][ci][co] | scale (Cout) | shift (Cout), where
+ * scale = gamma / sqrt(running_var + 1e-3) and shift = beta - running_mean * scale, computed in fp64 and rounded once.
+ * Synchronises the device (the blob is replaced under no running forward). */
+LWG_API size_t lwg_inception_weight_floats(void);
+LWG_API int lwg_inception_set_weights(lwg_inception *h, const float *blob_host, size_t n_floats);
+/* frames (n,3,H,W) fp32 NCHW -> features (n,2048) fp32.  mode: the pixel modes 0, 1, 2 of lwg_eval_pair_stats (1 is the
+ * reference's `out *= 2; out -= 1` on [0,1] frames), applied before the resize.  (out_h, out_w): (299, 299) resizes bilinearly with
+ * align_corners=False; (0, 0) feeds the frames as they are (the network is fully convolutional; its input must be at least 75 x 75).
+ * tap_stage: -1, or one of the 18 stages 0..17 = Conv2d_1a_3x3, Conv2d_2a_3x3, Conv2d_2b_3x3, the first max pool, Conv2d_3b_1x1,
+ * Conv2d_4a_3x3, the second max pool, Mixed_5b, 5c, 5d, 6a, 6b, 6c, 6d, 6e, 7a, 7b, 7c (the map the global pool reads), whose NHWC
+ * output (n,Hs,Ws,Cs) is copied to tap_out.
+ * A network input below 75 x 75: LWG_ERR_UNSUPPORTED; n > max_images, H > max_h, W > max_w or no weights set: LWG_ERR_STATE; a mode
+ * outside 0..2, another resize target, a tap_stage outside -1..17: LWG_ERR_INVALID_ARG. */
+LWG_API int lwg_inception_forward(lwg_inception *h, const float *frames, int n, int H, int W, int mode, int out_h, int out_w,
+                                  float *features, int tap_stage, float *tap_out, lwg_stream_t stream);
+/* Op-level entry points (what lwg_inception_forward is made of; the tests call them directly).  Every argument is checked before
+ * the first HIP call.
+ * conv (BasicConv2d, torchvision/models/inception.py): w (kh,kw,Cin,Cout) [kh][kw][ci][co]; scale, shift (Cout) or NULL (1 and 0);
+ *   y = relu?(fmaf(conv(x, w), scale, shift)) written to channels y_offset .. y_offset + Cout - 1 of the (N,Ho,Wo,y_pitch) NHWC
+ *   buffer y, the other channels untouched.  kh, kw in 1..11, one stride 1..4, ph < kh and pw < kw, all independent; Cout a
+ *   multiple of 4 (else LWG_ERR_UNSUPPORTED).  input_mode < 0: x is (N,H,W,Cin) NHWC as it is, Cin a multiple of 4 (else
+ *   LWG_ERR_UNSUPPORTED), 16-byte aligned; 0..2: x is (N,3,H,W) NCHW frames in that pixel mode.  w 16-byte aligned.
+ * maxpool: F.max_pool2d(kernel 3, stride 2), floor mode, no padding: (N,H,W,C) -> channels y_offset.. of (N,(H-3)/2+1,(W-3)/2+1,
+ *   y_pitch); C, y_pitch and y_offset multiples of 4, H, W >= 3.
+ * avgpool: F.avg_pool2d(kernel 3, stride 1, padding 1), count_include_pad=True: (N,H,W,C) -> (N,H,W,C); C a multiple of 4.
+ * global_pool: F.adaptive_avg_pool2d(x, 1): (N,P,C) -> (N,C), P = H*W pixels added in ascending order in fp64, rounded once. */
+LWG_API int lwg_inception_conv(const float *x, int N, int H, int W, int Cin, const float *w, const float *scale, const float *shift,
+                               int Cout, int kh, int kw, int stride, int ph, int pw, int relu, int input_mode, float *y, int y_pitch,
+                               int y_offset, lwg_stream_t stream);
+LWG_API int lwg_inception_maxpool(const float *x, int N, int H, int W, int C, float *y, int y_pitch, int y_offset,
+                                  lwg_stream_t stream);
+LWG_API int lwg_inception_avgpool(const float *x, int N, int H, int W, int C, float *y, lwg_stream_t stream);
+LWG_API int lwg_inception_global_pool(const float *x, int N, int P, int C, float *y, lwg_stream_t stream);
+
 /* ---- training, first slice: the PatchGAN discriminator update ---------------------------------
  * Replaces PatchDiscriminator.forward (networks/discriminator.py:8-57, norm_type='instance', use_sigmoid=False) and,
  * for the discriminator, ImpersonatorTrainer._optimize_D + loss.backward() + torch.optim.Adam.step()
