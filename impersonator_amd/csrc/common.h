@@ -77,4 +77,22 @@ inline int device_cu_count()
 inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// the device buffers of a network handle (hmr, lpips, inception)
+inline hipError_t alloc_floats(float **p, size_t n) { return hipMalloc(reinterpret_cast<void **>(p), n * sizeof(float)); }
+inline void free_device(void *p)
+{
+    if (p) (void)hipFree(p);
+}
+
+// replaces such a handle's weight blob; `ready` is false until the new one is whole
+inline int upload_blob(float *blob, const float *blob_host, size_t n_floats, bool &ready)
+{
+    ready = false;
+    // synchronous: the caller's host buffer may go away after the call, and no forward may overlap the replacement
+    LWG_HIP(hipDeviceSynchronize());
+    LWG_HIP(hipMemcpy(blob, blob_host, n_floats * sizeof(float), hipMemcpyHostToDevice));
+    ready = true;
+    return LWG_OK;
+}
+
 }  // namespace lwg

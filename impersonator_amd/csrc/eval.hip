@@ -9,9 +9,9 @@
 //          scikit-image does and takes the logarithm.
 //   SSPE : |d[0]|, sum |d[75:85]|, sum |d[0:75]| of d = pred_theta - ref_theta, per frame.
 //
-// Arithmetic.  A pixel is loaded and mapped in float32 (the three modes below, one rounding per step: the file is built without
-// fp contraction); everything after that is fp64: the products of two float32 values are exact there, so the window moments lose
-// nothing before the subtraction uxx - ux*ux that a float32 statement gets wrong on flat regions.
+// Arithmetic.  A pixel is loaded and mapped in float32 (the three modes of pixel.h's map_pixel, one rounding per step);
+// everything after that is fp64: the products of two float32 values are exact there, so the window moments lose nothing before
+// the subtraction uxx - ux*ux that a float32 statement gets wrong on flat regions.
 //
 // Tiling.  One workgroup of 256 lanes owns a 16x16 tile of one (frame, channel) plane: its pixels for the squared-difference sum
 // and min/max (every pixel belongs to exactly one tile), and the window positions whose top-left pixel lies in it for S.  It
@@ -20,6 +20,7 @@
 // one workgroup per frame, adds each channel's tiles in index order per lane and the lanes with the same tree.  No atomics, no
 // dependence on N or on the frame's position in the batch: a frame's four numbers are the same bits wherever it is scored.
 #include "common.h"
+#include "pixel.h"
 
 namespace lwg {
 namespace {
@@ -28,28 +29,6 @@ constexpr int kTile = 16;             // tile edge: 256 lanes, one window positi
 constexpr int kWin = 7;               // scikit-image's default win_size
 constexpr int kPatch = kTile + kWin - 1;
 constexpr int kStatsPerTile = 4;      // sum S, sum (pred-ref)^2, min ref, max ref
-
-// how a stored value becomes the value that is scored; every step a separately rounded float32 operation
-//   0: as it is   1: [0,1] -> [-1,1], 2*x - 1   2: [-1,1] through the writer's 8 bits and the loader's way back
-__device__ __forceinline__ float load_mapped(float x, int mode)
-{
-    if (mode == 1) {
-        const float t = 2.f * x;
-        return t - 1.f;
-    }
-    if (mode == 2) {
-        const float a = x + 1.f;
-        const float b = a / 2.f;
-        const float c = b * 255.f;
-        float u = truncf(c);
-        u = u > 0.f ? u : 0.f;         // NaN -> 0 as well
-        u = u < 255.f ? u : 255.f;
-        const float d = u / 255.f;
-        const float e = d * 2.f;
-        return e - 1.f;
-    }
-    return x;
-}
 
 // fixed-order reductions over the 256 lanes of a workgroup; the result is valid in lane 0
 template <class Op>
@@ -92,8 +71,8 @@ __global__ __launch_bounds__(256) void pair_stats_tiles_kernel(const float *__re
         const int y = y0 + py, x = x0 + px;
         float a = 0.f, b = 0.f;
         if (y < H && x < W) {
-            a = load_mapped(p[(size_t)y * W + x], mode);
-            b = load_mapped(r[(size_t)y * W + x], mode);
+            a = map_pixel(p[(size_t)y * W + x], mode);
+            b = map_pixel(r[(size_t)y * W + x], mode);
         }
         sp[py][px] = a;
         sr[py][px] = b;
@@ -203,20 +182,6 @@ __global__ __launch_bounds__(256) void pair_stats_finalize_kernel(const double *
         o[2] = mn;
         o[3] = mx;
     }
-}
-
-// ATen's source index of F.interpolate(mode='bilinear', align_corners=False), float32.  scale*(dst+0.5)-0.5 is ONE fused
-// multiply-add, stated as such: torch's CPU binaries contract it (measured: with two roundings the result is up to 5.7e-7 from
-// F.interpolate on [-1,1] noise, with the fused form 1.2e-7), and so do its device builds.  Everything else rounds per step.
-__device__ __forceinline__ void linear_taps(float scale, int dst, int in, int &i0, int &i1, float &w0, float &w1)
-{
-    const float c = (float)dst + 0.5f;
-    float src = fmaf(scale, c, -0.5f);
-    src = src > 0.f ? src : 0.f;
-    i0 = min((int)src, in - 1);
-    i1 = min(i0 + 1, in - 1);
-    w1 = fminf(fmaxf(src - (float)i0, 0.f), 1.f);
-    w0 = 1.f - w1;
 }
 
 __global__ __launch_bounds__(256) void resize_bilinear_kernel(const float *__restrict__ x, int H, int W, int Ho, int Wo,

@@ -5,9 +5,9 @@
 // tail (the maps are 112^2 ... 7^2: 49 pixels per image are no multiple of any tile).  Every convolution of the network
 // -- 38 1x1 GEMMs, 16 3x3 (13 stride 1, 3 stride 2) and the 7x7 stride-2 stem -- runs on ONE kernel:
 //
-//   hmr_conv_kernel: implicit GEMM on v_mfma_f32_32x32x2_f32 (bit-for-bit a k-ordered fmaf chain).  Workgroup = 64
-//   pixels x 64 output channels, four waves of one 32x32 tile, K = taps x Cin walked 32 at a time through a
-//   double-buffered LDS stage.  Optional PROLOGUE on the gathered input: per-input-channel max(x*scale + shift, 0)
+//   igemm32::conv_kernel<HmrVec> (Cin % 4 == 0) / <HmrScalar> (the stem): the implicit GEMM of igemm32.h on
+//   v_mfma_f32_32x32x2_f32, shared with lpips.hip and inception.hip; this file states what is HMR's own, as the policy
+//   struct HmrConv.  Optional PROLOGUE on the gathered input: per-input-channel max(x*scale + shift, 0)
 //   (bn1 + ReLU in front of conv1 and of the shortcut conv; padding taps stay 0, as torch pads the activated tensor).
 //   Optional EPILOGUE: + bias, per-output-channel max(v*scale + shift, 0) (bn2 / bn3 + ReLU), + residual read at
 //   (oh*rs, ow*rs) of an NHWC tensor (conv3 + shortcut; rs = 2 is the reference's subsample = max_pool2d([1,1], stride 2)).
@@ -20,159 +20,75 @@
 #include <vector>
 
 #include "common.h"
+#include "igemm32.h"
+#include "maxpool.h"
 
 namespace lwg {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int BM = 64, BN = 64, BK = 32;
-constexpr int A_PITCH = BK + 1;   // odd pitch: the 32 rows a fragment read touches fall into 32 banks
-constexpr int B_PITCH = BN;
-
-struct ConvP {
+// every convolution of the network: NHWC in, NHWC out.  The prologue and the epilogue of the file header, as a policy of
+// igemm32::conv_kernel; HmrVec and HmrScalar add the gather
+struct HmrConv {
+    igemm32::Geom g;
     const float *x;          // (N,H,W,Cin) NHWC
-    const float *w;          // (k*k*Cin, Cout): [tap][ci][co]
     const float *pre_scale, *pre_shift;     // (Cin) or NULL
     const float *bias;                      // (Cout) or NULL
     const float *post_scale, *post_shift;   // (Cout) or NULL
     const float *res;                       // (N,res_H,res_W,Cout) or NULL
     float *y;                // (N,Ho,Wo,Cout)
-    int N, H, W, Cin, Cout, ks, stride, pad, Ho, Wo;
     int res_stride, res_H, res_W;
-    long M;                  // N*Ho*Wo
-    int K;                   // ks*ks*Cin
+    static constexpr bool kCoutTail = false;
+
+    struct Col {
+        float bias, ps, pb;
+    };
+    __device__ Col column(int co) const
+    {
+        return Col{bias ? bias[co] : 0.f, post_scale ? post_scale[co] : 1.f, post_scale ? post_shift[co] : 0.f};
+    }
+    __device__ void write(long m, int co, const Col &c, float v) const
+    {
+        if (bias) v += c.bias;
+        if (post_scale) v = fmaxf(fmaf(v, c.ps, c.pb), 0.f);
+        if (res) {
+            const int n = (int)(m / ((long)g.Ho * g.Wo));
+            const int rem = (int)(m - (long)n * g.Ho * g.Wo);
+            const int oh = rem / g.Wo, ow = rem - oh * g.Wo;
+            v += res[(((size_t)n * res_H + (size_t)oh * res_stride) * res_W + (size_t)ow * res_stride) * g.Cout + co];
+        }
+        y[(size_t)m * g.Cout + co] = v;
+    }
 };
 
-// VEC: Cin % 4 == 0, so four consecutive reduction indices are one 16-byte load inside one tap
-template <bool VEC>
-__global__ __launch_bounds__(256) void hmr_conv_kernel(const ConvP p)
-{
-    __shared__ __attribute__((aligned(16))) float sA[2][BM * A_PITCH];
-    __shared__ __attribute__((aligned(16))) float sB[2][BK * B_PITCH];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const long m0 = (long)blockIdx.x * BM;
-    const int co0 = blockIdx.y * BN;
-
-    // A loader: rows (tid >> 3) and (tid >> 3) + 32, reduction indices (tid & 7) * 4 .. + 3 of the stage
-    const int a_col = (tid & 7) * 4;
-    int a_n[2], a_ih0[2], a_iw0[2];
-    bool a_ok[2];
-#pragma unroll
-    for (int v = 0; v < 2; ++v) {
-        const long m = m0 + (tid >> 3) + 32 * v;
-        a_ok[v] = m < p.M;
-        const long mm = a_ok[v] ? m : 0;
-        const int n = (int)(mm / ((long)p.Ho * p.Wo));
-        const int rem = (int)(mm - (long)n * p.Ho * p.Wo);
-        const int oh = rem / p.Wo, ow = rem - oh * p.Wo;
-        a_n[v] = n;
-        a_ih0[v] = oh * p.stride - p.pad;
-        a_iw0[v] = ow * p.stride - p.pad;
-    }
-    // B loader: reduction rows (tid >> 4) and (tid >> 4) + 16, output channels (tid & 15) * 4 .. + 3
-    const int b_col = (tid & 15) * 4;
-
-    float4 ra[2], rb[2];
-    auto gather1 = [&](int v, int kg) -> float {   // one input value, activated; 0 outside the image, past K or past M
-        if (!a_ok[v] || kg >= p.K) return 0.f;
-        const int tap = kg / p.Cin, c = kg - tap * p.Cin;
-        const int kh = tap / p.ks, kw = tap - kh * p.ks;
-        const int ih = a_ih0[v] + kh, iw = a_iw0[v] + kw;
-        if ((unsigned)ih >= (unsigned)p.H || (unsigned)iw >= (unsigned)p.W) return 0.f;
-        float val = p.x[(((size_t)a_n[v] * p.H + ih) * p.W + iw) * p.Cin + c];
-        if (p.pre_scale) val = fmaxf(fmaf(val, p.pre_scale[c], p.pre_shift[c]), 0.f);
-        return val;
-    };
-    auto load = [&](int k0) {
-        const int kg = k0 + a_col;
-#pragma unroll
-        for (int v = 0; v < 2; ++v) {
-            if (VEC) {
-                ra[v] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (a_ok[v] && kg < p.K) {
-                    const int tap = kg / p.Cin, c = kg - tap * p.Cin;
-                    const int kh = tap / p.ks, kw = tap - kh * p.ks;
-                    const int ih = a_ih0[v] + kh, iw = a_iw0[v] + kw;
-                    if ((unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W) {
-                        float4 val = *reinterpret_cast<const float4 *>(p.x + (((size_t)a_n[v] * p.H + ih) * p.W + iw) * p.Cin + c);
-                        if (p.pre_scale) {
-                            const float4 s = *reinterpret_cast<const float4 *>(p.pre_scale + c);
-                            const float4 b = *reinterpret_cast<const float4 *>(p.pre_shift + c);
-                            val.x = fmaxf(fmaf(val.x, s.x, b.x), 0.f);
-                            val.y = fmaxf(fmaf(val.y, s.y, b.y), 0.f);
-                            val.z = fmaxf(fmaf(val.z, s.z, b.z), 0.f);
-                            val.w = fmaxf(fmaf(val.w, s.w, b.w), 0.f);
-                        }
-                        ra[v] = val;
-                    }
-                }
-            } else {
-                ra[v] = make_float4(gather1(v, kg), gather1(v, kg + 1), gather1(v, kg + 2), gather1(v, kg + 3));
+// Cin % 4 == 0, so four consecutive reduction indices are one 16-byte load inside one tap
+struct HmrVec : HmrConv {
+    __device__ float4 gather(const igemm32::Row &r, int kg) const
+    {
+        return igemm32::gather_nhwc4(g, x, r, kg, [&](float4 val, int c) {
+            if (pre_scale) {
+                const float4 s = *reinterpret_cast<const float4 *>(pre_scale + c);
+                const float4 b = *reinterpret_cast<const float4 *>(pre_shift + c);
+                val.x = fmaxf(fmaf(val.x, s.x, b.x), 0.f);
+                val.y = fmaxf(fmaf(val.y, s.y, b.y), 0.f);
+                val.z = fmaxf(fmaf(val.z, s.z, b.z), 0.f);
+                val.w = fmaxf(fmaf(val.w, s.w, b.w), 0.f);
             }
-        }
-#pragma unroll
-        for (int v = 0; v < 2; ++v) {
-            const int kr = k0 + (tid >> 4) + 16 * v;
-            rb[v] = kr < p.K ? *reinterpret_cast<const float4 *>(p.w + (size_t)kr * p.Cout + co0 + b_col)
-                             : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    auto store = [&](int buf) {
-#pragma unroll
-        for (int v = 0; v < 2; ++v) {
-            float *d = &sA[buf][((tid >> 3) + 32 * v) * A_PITCH + a_col];
-            d[0] = ra[v].x;
-            d[1] = ra[v].y;
-            d[2] = ra[v].z;
-            d[3] = ra[v].w;
-            *reinterpret_cast<float4 *>(&sB[buf][((tid >> 4) + 16 * v) * B_PITCH + b_col]) = rb[v];
-        }
-    };
-
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-
-    int buf = 0;
-    load(0);
-    store(0);
-    __syncthreads();
-    for (int k0 = 0; k0 < p.K; k0 += BK) {
-        const bool more = k0 + BK < p.K;
-        if (more) load(k0 + BK);
-        // A: lane -> pixel row (lane & 31), k = lane >> 5;  B: lane -> output channel (lane & 31), k = lane >> 5
-        const float *ar = &sA[buf][(wm * 32 + (lane & 31)) * A_PITCH + (lane >> 5)];
-        const float *br = &sB[buf][(lane >> 5) * B_PITCH + wn * 32 + (lane & 31)];
-#pragma unroll
-        for (int kk = 0; kk < BK / 2; ++kk)
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ar[2 * kk], br[2 * kk * B_PITCH], acc, 0, 0, 0);
-        if (more) store(buf ^ 1);
-        __syncthreads();
-        buf ^= 1;
+            return val;
+        });
     }
+};
 
-    // C/D layout: col = lane & 31 -> output channel, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5) -> pixel
-    const int co = co0 + wn * 32 + (lane & 31);
-    const float bias = p.bias ? p.bias[co] : 0.f;
-    const float ps = p.post_scale ? p.post_scale[co] : 1.f, pb = p.post_scale ? p.post_shift[co] : 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const long m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        if (m >= p.M) continue;
-        float v = acc[r];
-        if (p.bias) v += bias;
-        if (p.post_scale) v = fmaxf(fmaf(v, ps, pb), 0.f);
-        if (p.res) {
-            const int n = (int)(m / ((long)p.Ho * p.Wo));
-            const int rem = (int)(m - (long)n * p.Ho * p.Wo);
-            const int oh = rem / p.Wo, ow = rem - oh * p.Wo;
-            v += p.res[(((size_t)n * p.res_H + (size_t)oh * p.res_stride) * p.res_W + (size_t)ow * p.res_stride) * p.Cout + co];
-        }
-        p.y[(size_t)m * p.Cout + co] = v;
+// any Cin (the 3-channel stem): one input value at a time, activated
+struct HmrScalar : HmrConv {
+    __device__ float4 gather(const igemm32::Row &r, int kg) const
+    {
+        return igemm32::gather_each(g, r, kg, g.Cin, [&](int c, int ih, int iw) {
+            float val = *igemm32::nhwc_at(g, x, r, c, ih, iw);
+            if (pre_scale) val = fmaxf(fmaf(val, pre_scale[c], pre_shift[c]), 0.f);
+            return val;
+        });
     }
-}
+};
 
 // (N,C,H,W) -> (N,H,W,C), C small (the 3-channel image in front of the stem)
 __global__ __launch_bounds__(256) void hmr_nhwc_kernel(const float *__restrict__ x, int C, long HW, long total, float *__restrict__ y)
@@ -183,36 +99,6 @@ __global__ __launch_bounds__(256) void hmr_nhwc_kernel(const float *__restrict__
     const long px = i / C;
     const long n = px / HW, hw = px - n * HW;
     y[i] = x[(n * C + c) * HW + hw];
-}
-
-// max_pool2d(kernel 3, stride 2, ceil_mode=True, no padding), NHWC, C % 4 == 0: taps outside the input are ignored
-__global__ __launch_bounds__(256) void hmr_maxpool_kernel(const float *__restrict__ x, int H, int W, int C4, int Ho, int Wo,
-                                                         long total, float *__restrict__ y)
-{
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;   // over N*Ho*Wo*C4
-    if (i >= total) return;
-    const int c4 = (int)(i % C4);
-    long px = i / C4;
-    const int ow = (int)(px % Wo);
-    px /= Wo;
-    const int oh = (int)(px % Ho);
-    const long n = px / Ho;
-    const float4 *xs = reinterpret_cast<const float4 *>(x);
-    float4 m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-    for (int kh = 0; kh < 3; ++kh) {
-        const int ih = oh * 2 + kh;
-        if (ih >= H) break;
-        for (int kw = 0; kw < 3; ++kw) {
-            const int iw = ow * 2 + kw;
-            if (iw >= W) break;
-            const float4 v = xs[((n * H + ih) * W + iw) * C4 + c4];
-            m.x = fmaxf(m.x, v.x);
-            m.y = fmaxf(m.y, v.y);
-            m.z = fmaxf(m.z, v.z);
-            m.w = fmaxf(m.w, v.w);
-        }
-    }
-    reinterpret_cast<float4 *>(y)[i] = m;
 }
 
 // relu(post_bn(x)) -> average over the HW pixels of an image: x (N,HW,C) -> out (N,C); pixels summed in ascending order
@@ -288,26 +174,16 @@ bool conv_geometry_ok(int k, int stride, int pad)
            (k == 7 && stride == 2 && pad == 3);
 }
 
-int launch_conv(ConvP p, hipStream_t st)
+int launch_conv(const HmrConv &p, hipStream_t st)
 {
-    p.Ho = (p.H + 2 * p.pad - p.ks) / p.stride + 1;
-    p.Wo = (p.W + 2 * p.pad - p.ks) / p.stride + 1;
-    p.M = (long)p.N * p.Ho * p.Wo;
-    p.K = p.ks * p.ks * p.Cin;
-    const dim3 grid((unsigned)ceil_div(p.M, BM), (unsigned)(p.Cout / BN));
-    if (p.Cin % 4 == 0) hmr_conv_kernel<true><<<grid, 256, 0, st>>>(p);
-    else hmr_conv_kernel<false><<<grid, 256, 0, st>>>(p);
-    LWG_LAUNCH_CHECK("hmr_conv_kernel");
-    return LWG_OK;
+    if (p.g.Cin % 4 == 0) return igemm32::launch(HmrVec{p}, "igemm32::conv_kernel<HmrVec>", st);
+    return igemm32::launch(HmrScalar{p}, "igemm32::conv_kernel<HmrScalar>", st);
 }
 
-int launch_maxpool(const float *x, int N, int H, int W, int C, float *y, hipStream_t st)
+// max_pool2d(3, 2, ceil_mode=True): taps outside the input are ignored
+int launch_ceil_maxpool(const float *x, int N, int H, int W, int C, float *y, hipStream_t st)
 {
-    const int Ho = ceil_div(H - 3, 2) + 1, Wo = ceil_div(W - 3, 2) + 1;
-    const long total = (long)N * Ho * Wo * (C / 4);
-    hmr_maxpool_kernel<<<ceil_div(total, 256), 256, 0, st>>>(x, H, W, C / 4, Ho, Wo, total, y);
-    LWG_LAUNCH_CHECK("hmr_maxpool_kernel");
-    return LWG_OK;
+    return launch_maxpool(x, N, H, W, C, pool_out_ceil(H), pool_out_ceil(W), y, C, 0, st);
 }
 
 int launch_pool(const float *x, int N, int HW, int C, const float *scale, const float *shift, float *out, hipStream_t st)
@@ -385,7 +261,7 @@ void build_plan(lwg_hmr *h)
     h->ops.push_back(stem);
     int H = kImage / 2;                                   // 112
     need(HB_STEM, (size_t)H * H * 64);
-    H = ceil_div(H - 3, 2) + 1;                           // 56
+    H = pool_out_ceil(H);                                 // 56
     need(HB_X0, (size_t)H * H * 64);
     int cur = HB_X0, Cin = 64;
     const int planes[4] = {64, 128, 256, 512}, layer_stride[4] = {2, 2, 2, 1};
@@ -393,7 +269,7 @@ void build_plan(lwg_hmr *h)
         const int p = planes[L];
         for (int i = 0; i < h->num_blocks[L]; ++i) {
             const int s = (i > 0 && i == h->num_blocks[L] - 1) ? layer_stride[L] : 1;   // hmr.py:140-147
-            const int Ho = (H + 2 - 3) / s + 1;
+            const int Ho = igemm32::conv_out(H, 3, s, 1);
             const bool shortcut = Cin != 4 * p;
             const int nxt = cur == HB_X0 ? HB_X1 : HB_X0;
             const long bn1 = take(2L * Cin);
@@ -457,13 +333,12 @@ int lwg_hmr_create(lwg_hmr **out, int max_batch, const int *num_blocks)
     h->max_batch = max_batch;
     for (int i = 0; i < 4; ++i) h->num_blocks[i] = nb[i];
     build_plan(h);
-    auto alloc = [&](float **p, size_t n) { return hipMalloc(reinterpret_cast<void **>(p), n * sizeof(float)); };
-    hipError_t e = alloc(&h->blob, h->blob_floats);
-    for (int r = 0; r < HB_COUNT && e == hipSuccess; ++r) e = alloc(&h->buf[r], h->buf_floats[r] * max_batch);
-    if (e == hipSuccess) e = alloc(&h->feat, (size_t)max_batch * kFeat);
-    if (e == hipSuccess) e = alloc(&h->h1, (size_t)max_batch * kHidden);
-    if (e == hipSuccess) e = alloc(&h->h2, (size_t)max_batch * kHidden);
-    if (e == hipSuccess) e = alloc(&h->theta, (size_t)max_batch * kTheta);
+    hipError_t e = alloc_floats(&h->blob, h->blob_floats);
+    for (int r = 0; r < HB_COUNT && e == hipSuccess; ++r) e = alloc_floats(&h->buf[r], h->buf_floats[r] * max_batch);
+    if (e == hipSuccess) e = alloc_floats(&h->feat, (size_t)max_batch * kFeat);
+    if (e == hipSuccess) e = alloc_floats(&h->h1, (size_t)max_batch * kHidden);
+    if (e == hipSuccess) e = alloc_floats(&h->h2, (size_t)max_batch * kHidden);
+    if (e == hipSuccess) e = alloc_floats(&h->theta, (size_t)max_batch * kTheta);
     if (e != hipSuccess) {
         lwg_hmr_destroy(h);
         LWG_FAIL(LWG_ERR_HIP, "lwg_hmr_create: hipMalloc failed: %s", hipGetErrorString(e));
@@ -475,10 +350,9 @@ int lwg_hmr_create(lwg_hmr **out, int max_batch, const int *num_blocks)
 void lwg_hmr_destroy(lwg_hmr *h)
 {
     if (!h) return;
-    auto fr = [](void *p) { if (p) (void)hipFree(p); };
-    fr(h->blob);
-    for (int r = 0; r < HB_COUNT; ++r) fr(h->buf[r]);
-    fr(h->feat); fr(h->h1); fr(h->h2); fr(h->theta);
+    free_device(h->blob);
+    for (int r = 0; r < HB_COUNT; ++r) free_device(h->buf[r]);
+    free_device(h->feat); free_device(h->h1); free_device(h->h2); free_device(h->theta);
     delete h;
 }
 
@@ -489,12 +363,7 @@ int lwg_hmr_set_weights(lwg_hmr *h, const float *blob_host, size_t n_floats)
     LWG_REQUIRE(h != nullptr, "lwg_hmr_set_weights: NULL handle");
     LWG_REQUIRE(blob_host != nullptr, "lwg_hmr_set_weights: NULL blob");
     LWG_REQUIRE(n_floats == h->blob_floats, "lwg_hmr_set_weights: blob of %zu floats, this network takes %zu", n_floats, h->blob_floats);
-    h->ready = false;
-    // synchronous: the caller's host buffer may go away after the call, and no forward may overlap the replacement
-    LWG_HIP(hipDeviceSynchronize());
-    LWG_HIP(hipMemcpy(h->blob, blob_host, n_floats * sizeof(float), hipMemcpyHostToDevice));
-    h->ready = true;
-    return LWG_OK;
+    return upload_blob(h->blob, blob_host, n_floats, h->ready);
 }
 
 int lwg_hmr_forward(lwg_hmr *h, const float *images, int n, int height, int width, float *theta_out, float *features_out,
@@ -513,20 +382,19 @@ int lwg_hmr_forward(lwg_hmr *h, const float *images, int n, int height, int widt
     LWG_LAUNCH_CHECK("hmr_nhwc_kernel");
     for (size_t i = 0; i < h->ops.size(); ++i) {
         const ConvOp &o = h->ops[i];
-        ConvP p;
+        HmrConv p;
         memset(&p, 0, sizeof(p));
+        p.g = igemm32::geom(h->blob + o.w, n, o.H, o.W, o.Cin, o.Cout, o.ks, o.ks, o.stride, o.pad, o.pad);
         p.x = h->buf[o.src];
         p.y = h->buf[o.dst];
-        p.w = h->blob + o.w;
         if (o.pre >= 0) { p.pre_scale = h->blob + o.pre; p.pre_shift = p.pre_scale + o.Cin; }
         if (o.bias >= 0) p.bias = h->blob + o.bias;
         if (o.post >= 0) { p.post_scale = h->blob + o.post; p.post_shift = p.post_scale + o.Cout; }
         if (o.res >= 0) { p.res = h->buf[o.res]; p.res_stride = o.res_stride; p.res_H = o.res_H; p.res_W = o.res_W; }
-        p.N = n; p.H = o.H; p.W = o.W; p.Cin = o.Cin; p.Cout = o.Cout; p.ks = o.ks; p.stride = o.stride; p.pad = o.pad;
         const int rc = launch_conv(p, st);
         if (rc != LWG_OK) return rc;
         if (i == 0) {
-            const int rc2 = launch_maxpool(h->buf[HB_STEM], n, kImage / 2, kImage / 2, 64, h->buf[HB_X0], st);
+            const int rc2 = launch_ceil_maxpool(h->buf[HB_STEM], n, kImage / 2, kImage / 2, 64, h->buf[HB_X0], st);
             if (rc2 != LWG_OK) return rc2;
         }
     }
@@ -551,7 +419,7 @@ int lwg_hmr_conv(const float *x, int N, int H, int W, int Cin, const float *w, i
     LWG_REQUIRE(x != nullptr && w != nullptr && y != nullptr, "lwg_hmr_conv: NULL x, w or y");
     LWG_REQUIRE(N >= 1 && H >= 1 && W >= 1 && Cin >= 1 && Cout >= 1, "lwg_hmr_conv: non-positive size");
     // 16-byte accesses: the weight rows always, the input and the prologue vectors when Cin is a multiple of 4
-    LWG_REQUIRE((reinterpret_cast<uintptr_t>(w) & 15) == 0, "lwg_hmr_conv: w is not 16-byte aligned");
+    LWG_REQUIRE(igemm32::aligned16(w), "lwg_hmr_conv: w is not 16-byte aligned");
     LWG_REQUIRE(Cin % 4 != 0 || ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(pre_scale) |
                                   reinterpret_cast<uintptr_t>(pre_shift)) & 15) == 0,
                 "lwg_hmr_conv: x / pre_scale / pre_shift are not 16-byte aligned");
@@ -559,22 +427,21 @@ int lwg_hmr_conv(const float *x, int N, int H, int W, int Cin, const float *w, i
     LWG_REQUIRE((post_scale == nullptr) == (post_shift == nullptr), "lwg_hmr_conv: the epilogue needs both scale and shift (one is NULL)");
     if (!conv_geometry_ok(k, stride, pad))
         LWG_FAIL(LWG_ERR_UNSUPPORTED, "lwg_hmr_conv: (k, stride, pad) = (%d, %d, %d) is none of (1,1,0) (3,1,1) (3,2,1) (7,2,3)", k, stride, pad);
-    if (Cout % lwg::BN != 0) LWG_FAIL(LWG_ERR_UNSUPPORTED, "lwg_hmr_conv: Cout = %d is no multiple of %d", Cout, lwg::BN);
-    if ((long)N * H * W * (long)(Cin > Cout ? Cin : Cout) >= (1L << 40))
-        LWG_FAIL(LWG_ERR_UNSUPPORTED, "lwg_hmr_conv: tensor too large");
-    const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
+    if (Cout % igemm32::BN != 0) LWG_FAIL(LWG_ERR_UNSUPPORTED, "lwg_hmr_conv: Cout = %d is no multiple of %d", Cout, igemm32::BN);
+    if (igemm32::too_large(N, H, W, Cin > Cout ? Cin : Cout)) LWG_FAIL(LWG_ERR_UNSUPPORTED, "lwg_hmr_conv: tensor too large");
+    const int Ho = igemm32::conv_out(H, k, stride, pad), Wo = igemm32::conv_out(W, k, stride, pad);
     LWG_REQUIRE(Ho >= 1 && Wo >= 1, "lwg_hmr_conv: empty output");
     if (residual) {
         LWG_REQUIRE(res_stride >= 1 && res_H >= 1 && res_W >= 1, "lwg_hmr_conv: residual stride / size not positive");
         LWG_REQUIRE((long)(Ho - 1) * res_stride < res_H && (long)(Wo - 1) * res_stride < res_W,
                     "lwg_hmr_conv: a %d x %d residual read with stride %d does not cover the %d x %d output", res_H, res_W, res_stride, Ho, Wo);
     }
-    ConvP p;
+    HmrConv p;
     memset(&p, 0, sizeof(p));
-    p.x = x; p.w = w; p.y = y;
+    p.g = igemm32::geom(w, N, H, W, Cin, Cout, k, k, stride, pad, pad);
+    p.x = x; p.y = y;
     p.pre_scale = pre_scale; p.pre_shift = pre_shift; p.bias = bias; p.post_scale = post_scale; p.post_shift = post_shift;
     p.res = residual; p.res_stride = res_stride; p.res_H = res_H; p.res_W = res_W;
-    p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.ks = k; p.stride = stride; p.pad = pad;
     return launch_conv(p, as_stream(stream));
 }
 
@@ -583,8 +450,8 @@ int lwg_hmr_maxpool(const float *x, int N, int H, int W, int C, float *y, lwg_st
     LWG_REQUIRE(x != nullptr && y != nullptr, "lwg_hmr_maxpool: NULL x or y");
     LWG_REQUIRE(N >= 1 && H >= 3 && W >= 3 && C >= 1, "lwg_hmr_maxpool: needs N, C >= 1 and H, W >= 3");
     if (C % 4 != 0) LWG_FAIL(LWG_ERR_UNSUPPORTED, "lwg_hmr_maxpool: C = %d is no multiple of 4", C);
-    LWG_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0, "lwg_hmr_maxpool: x / y are not 16-byte aligned");
-    return launch_maxpool(x, N, H, W, C, y, as_stream(stream));
+    LWG_REQUIRE(igemm32::aligned16(x) && igemm32::aligned16(y), "lwg_hmr_maxpool: x / y are not 16-byte aligned");
+    return launch_ceil_maxpool(x, N, H, W, C, y, as_stream(stream));
 }
 
 int lwg_hmr_pool_features(const float *x, int N, int HW, int C, const float *scale, const float *shift, float *out,

@@ -4,15 +4,14 @@
 //
 // 94 x (Conv2d(bias=False) + BatchNorm2d(eps=1e-3, eval) + ReLU), two MaxPool(3,2), nine avg_pool2d(3,1,1), a global average pool.
 //
-//   inception_conv_kernel: implicit GEMM on v_mfma_f32_32x32x2_f32 (bit-for-bit a k-ordered fmaf chain), exact fp32, the tiling of
-//   lpips_conv_kernel: workgroup = 64 pixels x 64 output channels, four waves of one 32x32 tile, K = taps x Cin walked 32 at a
-//   time through a double-buffered LDS stage; M = N*Ho*Wo flattened across images and predicated at its tail.  kh, kw, stride, ph
-//   and pw are independent; Cout is predicated (48, 80, 320, 448 occur); the output goes to a channel offset with a channel pitch,
-//   so the branches of a Mixed block write their slices of the concatenated buffer themselves.  Epilogue: fmaf(acc, scale, shift),
-//   the BatchNorm folded on the host in fp64 and rounded once to fp32, then ReLU.  The first convolution reads the (n,3,H,W) NCHW
-//   frames through the evaluator's pixel modes.
+//   igemm32::conv_kernel<InceptionFrames> / <InceptionNhwc>: the exact-fp32 implicit GEMM of igemm32.h on v_mfma_f32_32x32x2_f32,
+//   shared with hmr.hip and lpips.hip; this file states what is Inception's own, as the policy struct InceptionConv.  kh, kw,
+//   stride, ph and pw are independent; Cout is predicated (48, 80, 320, 448 occur); the output goes to a channel offset with a
+//   channel pitch, so the branches of a Mixed block write their slices of the concatenated buffer themselves.  Epilogue:
+//   fmaf(acc, scale, shift), the BatchNorm folded on the host in fp64 and rounded once to fp32, then ReLU.  The first convolution
+//   reads the (n,3,H,W) NCHW frames through the evaluator's pixel modes (map_pixel of pixel.h).
 //
-//   inception_maxpool_kernel: F.max_pool2d(3, 2), floor mode, NHWC, into a channel slice.
+//   maxpool3s2_kernel (maxpool.h) at floor-mode sizes: F.max_pool2d(3, 2), NHWC, into a channel slice.
 //   inception_avgpool_kernel: F.avg_pool2d(3, 1, 1), count_include_pad=True: the nine taps added in (kh, kw) order, padded taps 0,
 //   divided by 9.
 //   inception_global_pool_kernel: the mean over the pixels, added in ascending pixel order in fp64, rounded once.
@@ -24,194 +23,51 @@
 #include <cstring>
 
 #include "common.h"
+#include "igemm32.h"
+#include "maxpool.h"
+#include "pixel.h"
 
 namespace lwg {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int BM = 64, BN = 64, BK = 32;
-constexpr int A_PITCH = BK + 1;   // odd pitch: the 32 rows a fragment read touches fall into 32 banks
-constexpr int B_PITCH = BN;
-
-// how a stored pixel becomes the value that is scored: the three modes of eval.hip's load_mapped, restated (that file's and
-// lpips.hip's results must not move, so nothing is shared with them); every step a separately rounded float32 operation
-//   0: as it is   1: [0,1] -> [-1,1], 2*x - 1   2: [-1,1] through the writer's 8 bits and the loader's way back
-__device__ __forceinline__ float map_pixel(float x, int mode)
-{
-    if (mode == 1) {
-        const float t = 2.f * x;
-        return t - 1.f;
-    }
-    if (mode == 2) {
-        const float a = x + 1.f;
-        const float b = a / 2.f;
-        const float c = b * 255.f;
-        float u = truncf(c);
-        u = u > 0.f ? u : 0.f;         // NaN -> 0 as well
-        u = u < 255.f ? u : 255.f;
-        const float d = u / 255.f;
-        const float e = d * 2.f;
-        return e - 1.f;
-    }
-    return x;
-}
-
-struct ConvP {
-    const float *x;          // NHWC (N,H,W,Cin); IMAGE: (N,3,H,W) NCHW frames
-    const float *w;          // (kh*kw*Cin, Cout): [kh][kw][ci][co]
+// Conv2d(bias=False) + BatchNorm + ReLU into a channel slice, as a policy of igemm32::conv_kernel; InceptionFrames and InceptionNhwc
+// add the gather
+struct InceptionConv {
+    igemm32::Geom g;
+    const float *x;          // NHWC (N,H,W,Cin); InceptionFrames: (N,3,H,W) NCHW frames
     const float *scale;      // (Cout) or NULL
     const float *shift;      // (Cout) or NULL
     float *y;                // (N,Ho,Wo,y_pitch), this convolution's channels at y_off
-    int N, H, W, Cin, Cout, kh, kw, stride, ph, pw, Ho, Wo, relu, mode, y_pitch, y_off;
-    long M;                  // N*Ho*Wo
-    int K;                   // kh*kw*Cin
+    int relu, mode, y_pitch, y_off;
+    static constexpr bool kCoutTail = true;   // 48, 80, 320, 448 occur
+
+    struct Col {
+        float scale, shift;
+    };
+    __device__ Col column(int co) const { return Col{scale ? scale[co] : 1.f, shift ? shift[co] : 0.f}; }
+    __device__ void write(long m, int co, const Col &c, float v) const
+    {
+        if (scale || shift) v = fmaf(v, c.scale, c.shift);   // one rounding
+        if (relu) v = fmaxf(v, 0.f);
+        y[(size_t)m * y_pitch + y_off + co] = v;
+    }
 };
 
-// IMAGE false: Cin % 4 == 0, four consecutive reduction indices are one 16-byte load inside one tap;
-// IMAGE true: Cin == 3, NCHW frames through map_pixel
-template <bool IMAGE>
-__global__ __launch_bounds__(256) void inception_conv_kernel(const ConvP p)
-{
-    __shared__ __attribute__((aligned(16))) float sA[2][BM * A_PITCH];
-    __shared__ __attribute__((aligned(16))) float sB[2][BK * B_PITCH];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const long m0 = (long)blockIdx.x * BM;
-    const int co0 = blockIdx.y * BN;
-
-    // A loader: rows (tid >> 3) and (tid >> 3) + 32, reduction indices (tid & 7) * 4 .. + 3 of the stage
-    const int a_col = (tid & 7) * 4;
-    int a_ih0[2], a_iw0[2];
-    const float *a_base[2];
-    bool a_ok[2];
-#pragma unroll
-    for (int v = 0; v < 2; ++v) {
-        const long m = m0 + (tid >> 3) + 32 * v;
-        a_ok[v] = m < p.M;
-        const long mm = a_ok[v] ? m : 0;
-        const int n = (int)(mm / ((long)p.Ho * p.Wo));
-        const int rem = (int)(mm - (long)n * p.Ho * p.Wo);
-        const int oh = rem / p.Wo, ow = rem - oh * p.Wo;
-        a_ih0[v] = oh * p.stride - p.ph;
-        a_iw0[v] = ow * p.stride - p.pw;
-        a_base[v] = p.x + (size_t)n * p.H * p.W * p.Cin;
+// Cin == 3, NCHW frames through map_pixel
+struct InceptionFrames : InceptionConv {
+    __device__ float4 gather(const igemm32::Row &r, int kg) const
+    {
+        const float *base = x + (size_t)r.n * g.H * g.W * g.Cin;
+        return igemm32::gather_each(g, r, kg, 3, [&](int c, int ih, int iw) {
+            return map_pixel(base[((size_t)c * g.H + ih) * g.W + iw], mode);
+        });
     }
-    // B loader: reduction rows (tid >> 4) and (tid >> 4) + 16, output channels (tid & 15) * 4 .. + 3 (Cout % 4 == 0)
-    const int b_col = (tid & 15) * 4;
-    const bool b_ok = co0 + b_col < p.Cout;
+};
 
-    float4 ra[2], rb[2];
-    auto gather1 = [&](int v, int kg) -> float {   // IMAGE: one mapped pixel; 0 outside the image, past K or past M
-        if (!a_ok[v] || kg >= p.K) return 0.f;
-        const int tap = kg / 3, c = kg - tap * 3;
-        const int kh = tap / p.kw, kw = tap - kh * p.kw;
-        const int ih = a_ih0[v] + kh, iw = a_iw0[v] + kw;
-        if ((unsigned)ih >= (unsigned)p.H || (unsigned)iw >= (unsigned)p.W) return 0.f;
-        return map_pixel(a_base[v][((size_t)c * p.H + ih) * p.W + iw], p.mode);
-    };
-    auto load = [&](int k0) {
-        const int kg = k0 + a_col;
-        if (IMAGE) {
-#pragma unroll
-            for (int v = 0; v < 2; ++v) ra[v] = make_float4(gather1(v, kg), gather1(v, kg + 1), gather1(v, kg + 2), gather1(v, kg + 3));
-        } else {
-            const int tap = kg / p.Cin, c = kg - tap * p.Cin;
-            const int kh = tap / p.kw, kw = tap - kh * p.kw;
-#pragma unroll
-            for (int v = 0; v < 2; ++v) {
-                ra[v] = make_float4(0.f, 0.f, 0.f, 0.f);
-                const int ih = a_ih0[v] + kh, iw = a_iw0[v] + kw;
-                if (a_ok[v] && kg < p.K && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W)
-                    ra[v] = *reinterpret_cast<const float4 *>(a_base[v] + ((size_t)ih * p.W + iw) * p.Cin + c);
-            }
-        }
-#pragma unroll
-        for (int v = 0; v < 2; ++v) {
-            const int kr = k0 + (tid >> 4) + 16 * v;
-            rb[v] = (b_ok && kr < p.K) ? *reinterpret_cast<const float4 *>(p.w + (size_t)kr * p.Cout + co0 + b_col)
-                                       : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    auto store = [&](int buf) {
-#pragma unroll
-        for (int v = 0; v < 2; ++v) {
-            float *d = &sA[buf][((tid >> 3) + 32 * v) * A_PITCH + a_col];
-            d[0] = ra[v].x;
-            d[1] = ra[v].y;
-            d[2] = ra[v].z;
-            d[3] = ra[v].w;
-            *reinterpret_cast<float4 *>(&sB[buf][((tid >> 4) + 16 * v) * B_PITCH + b_col]) = rb[v];
-        }
-    };
-
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-
-    int buf = 0;
-    load(0);
-    store(0);
-    __syncthreads();
-    for (int k0 = 0; k0 < p.K; k0 += BK) {
-        const bool more = k0 + BK < p.K;
-        if (more) load(k0 + BK);
-        // A: lane -> pixel row (lane & 31), k = lane >> 5;  B: lane -> output channel (lane & 31), k = lane >> 5
-        const float *ar = &sA[buf][(wm * 32 + (lane & 31)) * A_PITCH + (lane >> 5)];
-        const float *br = &sB[buf][(lane >> 5) * B_PITCH + wn * 32 + (lane & 31)];
-#pragma unroll
-        for (int kk = 0; kk < BK / 2; ++kk)
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ar[2 * kk], br[2 * kk * B_PITCH], acc, 0, 0, 0);
-        if (more) store(buf ^ 1);
-        __syncthreads();
-        buf ^= 1;
-    }
-
-    // C/D layout: col = lane & 31 -> output channel, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5) -> pixel
-    const int co = co0 + wn * 32 + (lane & 31);
-    if (co >= p.Cout) return;
-    const float scale = p.scale ? p.scale[co] : 1.f;
-    const float shift = p.shift ? p.shift[co] : 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const long m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        if (m >= p.M) continue;
-        float v = acc[r];
-        if (p.scale || p.shift) v = fmaf(v, scale, shift);   // one rounding
-        if (p.relu) v = fmaxf(v, 0.f);
-        p.y[(size_t)m * p.y_pitch + p.y_off + co] = v;
-    }
-}
-
-// max_pool2d(kernel 3, stride 2), floor mode, no padding, NHWC, C % 4 == 0: every window lies inside the input.
-// pitch4 / off4: the output's channel pitch and offset in float4 units
-__global__ __launch_bounds__(256) void inception_maxpool_kernel(const float *__restrict__ x, int H, int W, int C4, int Ho, int Wo,
-                                                               long total, float *__restrict__ y, int pitch4, int off4)
-{
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;   // over N*Ho*Wo*C4
-    if (i >= total) return;
-    const int c4 = (int)(i % C4);
-    const long opx = i / C4;
-    long px = opx;
-    const int ow = (int)(px % Wo);
-    px /= Wo;
-    const int oh = (int)(px % Ho);
-    const long n = px / Ho;
-    const float4 *xs = reinterpret_cast<const float4 *>(x);
-    float4 m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-#pragma unroll
-    for (int kh = 0; kh < 3; ++kh) {
-#pragma unroll
-        for (int kw = 0; kw < 3; ++kw) {
-            const float4 v = xs[((n * H + (oh * 2 + kh)) * W + (ow * 2 + kw)) * C4 + c4];
-            m.x = fmaxf(m.x, v.x);
-            m.y = fmaxf(m.y, v.y);
-            m.z = fmaxf(m.z, v.z);
-            m.w = fmaxf(m.w, v.w);
-        }
-    }
-    reinterpret_cast<float4 *>(y)[opx * pitch4 + off4 + c4] = m;
-}
+// Cin % 4 == 0, four consecutive reduction indices are one 16-byte load inside one tap
+struct InceptionNhwc : InceptionConv {
+    __device__ float4 gather(const igemm32::Row &r, int kg) const { return igemm32::gather_nhwc4(g, x, r, kg); }
+};
 
 // avg_pool2d(kernel 3, stride 1, padding 1), count_include_pad=True, NHWC, C % 4 == 0: the taps inside the image added in
 // (kh, kw) order (a padded tap is a zero, which changes no sum), then a true division by 9
@@ -258,19 +114,6 @@ __global__ __launch_bounds__(256) void inception_global_pool_kernel(const float 
     y[i] = (float)(s / (double)P);
 }
 
-// ATen's source index of F.interpolate(mode='bilinear', align_corners=False), float32, as eval.hip states it:
-// scale*(dst+0.5)-0.5 is ONE fused multiply-add; everything else rounds per step
-__device__ __forceinline__ void linear_taps(float scale, int dst, int in, int &i0, int &i1, float &w0, float &w1)
-{
-    const float c = (float)dst + 0.5f;
-    float src = fmaf(scale, c, -0.5f);
-    src = src > 0.f ? src : 0.f;
-    i0 = min((int)src, in - 1);
-    i1 = min(i0 + 1, in - 1);
-    w1 = fminf(fmaxf(src - (float)i0, 0.f), 1.f);
-    w0 = 1.f - w1;
-}
-
 // frames (N,3,H,W) -> (N,3,Ho,Wo): the pixel mode first (the reference's `out *= 2; out -= 1`), then the resize
 __global__ __launch_bounds__(256) void inception_prep_kernel(const float *__restrict__ x, int H, int W, int Ho, int Wo, int mode,
                                                             long total, float *__restrict__ y)
@@ -292,30 +135,19 @@ __global__ __launch_bounds__(256) void inception_prep_kernel(const float *__rest
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-inline int conv_out(int in, int k, int stride, int pad) { return in + 2 * pad >= k ? (in + 2 * pad - k) / stride + 1 : 0; }
-inline int pool_out(int in) { return in >= 3 ? (in - 3) / 2 + 1 : 0; }
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+using igemm32::aligned16;
+using igemm32::conv_out;
 
-int launch_conv(ConvP p, bool image, hipStream_t st)
+int launch_conv(const InceptionConv &p, bool image, hipStream_t st)
 {
-    p.Ho = conv_out(p.H, p.kh, p.stride, p.ph);
-    p.Wo = conv_out(p.W, p.kw, p.stride, p.pw);
-    p.M = (long)p.N * p.Ho * p.Wo;
-    p.K = p.kh * p.kw * p.Cin;
-    const dim3 grid((unsigned)ceil_div(p.M, BM), (unsigned)ceil_div(p.Cout, BN));
-    if (image) inception_conv_kernel<true><<<grid, 256, 0, st>>>(p);
-    else inception_conv_kernel<false><<<grid, 256, 0, st>>>(p);
-    LWG_LAUNCH_CHECK("inception_conv_kernel");
-    return LWG_OK;
+    if (image) return igemm32::launch(InceptionFrames{p}, "igemm32::conv_kernel<InceptionFrames>", st);
+    return igemm32::launch(InceptionNhwc{p}, "igemm32::conv_kernel<InceptionNhwc>", st);
 }
 
-int launch_maxpool(const float *x, int N, int H, int W, int C, float *y, int pitch, int off, hipStream_t st)
+// F.max_pool2d(3, 2), floor mode, into a channel slice
+int launch_floor_maxpool(const float *x, int N, int H, int W, int C, float *y, int pitch, int off, hipStream_t st)
 {
-    const int Ho = pool_out(H), Wo = pool_out(W);
-    const long total = (long)N * Ho * Wo * (C / 4);
-    inception_maxpool_kernel<<<ceil_div(total, 256), 256, 0, st>>>(x, H, W, C / 4, Ho, Wo, total, y, pitch / 4, off / 4);
-    LWG_LAUNCH_CHECK("inception_maxpool_kernel");
-    return LWG_OK;
+    return launch_maxpool(x, N, H, W, C, pool_out(H), pool_out(W), y, pitch, off, st);
 }
 
 int launch_avgpool(const float *x, int N, int H, int W, int C, float *y, hipStream_t st)
@@ -528,10 +360,9 @@ int lwg_inception_create(lwg_inception **out, int max_images, int max_h, int max
     h->max_w = max_w;
     // a frame is either resized to 299 x 299 or taken as it is: the network input is at most the larger of the two
     Walker(h->plan).network(max_h > kNetSize ? max_h : kNetSize, max_w > kNetSize ? max_w : kNetSize);
-    auto alloc = [&](float **p, size_t n) { return hipMalloc(reinterpret_cast<void **>(p), n * sizeof(float)); };
-    hipError_t e = alloc(&h->blob, (size_t)h->plan.blob_floats);
-    for (int b = 0; b < NBUF && e == hipSuccess; ++b) e = alloc(&h->buf[b], (size_t)max_images * h->plan.need[b]);
-    if (e == hipSuccess) e = alloc(&h->resized, (size_t)max_images * 3 * kNetSize * kNetSize);
+    hipError_t e = alloc_floats(&h->blob, (size_t)h->plan.blob_floats);
+    for (int b = 0; b < NBUF && e == hipSuccess; ++b) e = alloc_floats(&h->buf[b], (size_t)max_images * h->plan.need[b]);
+    if (e == hipSuccess) e = alloc_floats(&h->resized, (size_t)max_images * 3 * kNetSize * kNetSize);
     if (e != hipSuccess) {
         lwg_inception_destroy(h);
         LWG_FAIL(LWG_ERR_HIP, "lwg_inception_create: hipMalloc failed: %s", hipGetErrorString(e));
@@ -543,10 +374,9 @@ int lwg_inception_create(lwg_inception **out, int max_images, int max_h, int max
 void lwg_inception_destroy(lwg_inception *h)
 {
     if (!h) return;
-    auto fr = [](void *p) { if (p) (void)hipFree(p); };
-    fr(h->blob);
-    for (int b = 0; b < NBUF; ++b) fr(h->buf[b]);
-    fr(h->resized);
+    free_device(h->blob);
+    for (int b = 0; b < NBUF; ++b) free_device(h->buf[b]);
+    free_device(h->resized);
     delete h;
 }
 
@@ -563,12 +393,7 @@ int lwg_inception_set_weights(lwg_inception *h, const float *blob_host, size_t n
     LWG_REQUIRE(blob_host != nullptr, "lwg_inception_set_weights: NULL blob");
     LWG_REQUIRE(n_floats == (size_t)h->plan.blob_floats, "lwg_inception_set_weights: blob of %zu floats, this network takes %ld", n_floats,
                 h->plan.blob_floats);
-    h->ready = false;
-    // synchronous: the caller's host buffer may go away after the call, and no forward may overlap the replacement
-    LWG_HIP(hipDeviceSynchronize());
-    LWG_HIP(hipMemcpy(h->blob, blob_host, n_floats * sizeof(float), hipMemcpyHostToDevice));
-    h->ready = true;
-    return LWG_OK;
+    return upload_blob(h->blob, blob_host, n_floats, h->ready);
 }
 
 int lwg_inception_forward(lwg_inception *h, const float *frames, int n, int H, int W, int mode, int out_h, int out_w, float *features,
@@ -613,18 +438,17 @@ int lwg_inception_forward(lwg_inception *h, const float *frames, int n, int H, i
         int rc = LWG_OK;
         if (o.kind == OP_CONV) {
             const ConvDef &d = plan.convs[o.conv];
-            ConvP p;
+            InceptionConv p;
             memset(&p, 0, sizeof(p));
+            p.g = igemm32::geom(h->blob + d.w_off, n, o.H, o.W, d.cin, d.cout, d.kh, d.kw, d.stride, d.ph, d.pw);
             p.x = src_of(o.src);
-            p.w = h->blob + d.w_off;
-            p.scale = p.w + (size_t)d.kh * d.kw * d.cin * d.cout;
+            p.scale = p.g.w + (size_t)d.kh * d.kw * d.cin * d.cout;
             p.shift = p.scale + d.cout;
             p.y = h->buf[o.dst];
-            p.N = n; p.H = o.H; p.W = o.W; p.Cin = d.cin; p.Cout = d.cout; p.kh = d.kh; p.kw = d.kw; p.stride = d.stride; p.ph = d.ph; p.pw = d.pw;
             p.relu = 1; p.mode = in_mode; p.y_pitch = o.pitch; p.y_off = o.off;
             rc = launch_conv(p, o.src == BUF_IN, st);
         } else if (o.kind == OP_MAXPOOL) {
-            rc = launch_maxpool(src_of(o.src), n, o.H, o.W, o.C, h->buf[o.dst], o.pitch, o.off, st);
+            rc = launch_floor_maxpool(src_of(o.src), n, o.H, o.W, o.C, h->buf[o.dst], o.pitch, o.off, st);
         } else {
             rc = launch_avgpool(src_of(o.src), n, o.H, o.W, o.C, h->buf[o.dst], st);
         }
@@ -661,13 +485,12 @@ int lwg_inception_conv(const float *x, int N, int H, int W, int Cin, const float
     if (Cout % 4 != 0) LWG_FAIL(LWG_ERR_UNSUPPORTED, "lwg_inception_conv: Cout = %d is no multiple of 4", Cout);
     const int Ho = conv_out(H, kh, stride, ph), Wo = conv_out(W, kw, stride, pw);
     LWG_REQUIRE(Ho >= 1 && Wo >= 1, "lwg_inception_conv: empty output");
-    if ((long)N * H * W * (long)Cin >= (1L << 40) || (long)N * Ho * Wo * (long)y_pitch >= (1L << 40) || (long)kh * kw * Cin > 0x7fffffffL ||
-        ((long)N * Ho * Wo + lwg::BM - 1) / lwg::BM > 0x7fffffffL)
+    if (igemm32::too_large(N, H, W, Cin) || igemm32::too_large(N, Ho, Wo, y_pitch) || igemm32::grid_too_large(N, Ho, Wo, kh, kw, Cin))
         LWG_FAIL(LWG_ERR_UNSUPPORTED, "lwg_inception_conv: tensor too large");
-    ConvP p;
+    InceptionConv p;
     memset(&p, 0, sizeof(p));
-    p.x = x; p.w = w; p.scale = scale; p.shift = shift; p.y = y;
-    p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.kh = kh; p.kw = kw; p.stride = stride; p.ph = ph; p.pw = pw;
+    p.g = igemm32::geom(w, N, H, W, Cin, Cout, kh, kw, stride, ph, pw);
+    p.x = x; p.scale = scale; p.shift = shift; p.y = y;
     p.relu = relu; p.mode = input_mode < 0 ? 0 : input_mode; p.y_pitch = y_pitch; p.y_off = y_offset;
     return launch_conv(p, input_mode >= 0, as_stream(stream));
 }
@@ -681,9 +504,9 @@ int lwg_inception_maxpool(const float *x, int N, int H, int W, int C, float *y, 
     if (C % 4 != 0 || y_pitch % 4 != 0 || y_offset % 4 != 0)
         LWG_FAIL(LWG_ERR_UNSUPPORTED, "lwg_inception_maxpool: C = %d, pitch %d, offset %d are not all multiples of 4", C, y_pitch, y_offset);
     LWG_REQUIRE(aligned16(x) && aligned16(y), "lwg_inception_maxpool: x / y are not 16-byte aligned");
-    if ((long)N * H * W * (C / 4) > 256L * 0x7fffffffL || (long)N * pool_out(H) * pool_out(W) * (long)y_pitch >= (1L << 40))
+    if ((long)N * H * W * (C / 4) > 256L * 0x7fffffffL || igemm32::too_large(N, pool_out(H), pool_out(W), y_pitch))
         LWG_FAIL(LWG_ERR_UNSUPPORTED, "lwg_inception_maxpool: tensor too large");
-    return launch_maxpool(x, N, H, W, C, y, y_pitch, y_offset, as_stream(stream));
+    return launch_floor_maxpool(x, N, H, W, C, y, y_pitch, y_offset, as_stream(stream));
 }
 
 int lwg_inception_avgpool(const float *x, int N, int H, int W, int C, float *y, lwg_stream_t stream)

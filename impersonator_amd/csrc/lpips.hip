@@ -4,15 +4,15 @@
 // The network is torchvision's alexnet().features[0:12]: conv 3->64 k11 s4 p2, ReLU, MaxPool(3,2), conv 64->192 k5 p2, ReLU,
 // MaxPool(3,2), conv 192->384 k3 p1, ReLU, conv 384->256 k3 p1, ReLU, conv 256->256 k3 p1, ReLU, with a tap after each ReLU.
 //
-//   lpips_conv_kernel: implicit GEMM on v_mfma_f32_32x32x2_f32 (bit-for-bit a k-ordered fmaf chain), exact fp32.  Workgroup = 64
-//   pixels x 64 output channels, four waves of one 32x32 tile, K = taps x Cin walked 32 at a time through a double-buffered LDS
-//   stage; the pixel dimension M = N*Ho*Wo is flattened across images and predicated at its tail.  Bias + ReLU in the epilogue.
+//   igemm32::conv_kernel<LpipsFrames> / <LpipsNhwc4> / <LpipsNhwc>: the exact-fp32 implicit GEMM of igemm32.h on
+//   v_mfma_f32_32x32x2_f32, shared with hmr.hip and inception.hip; this file states what is LPIPS's own, as the policy struct
+//   LpipsConv.  Bias + ReLU in the epilogue.
 //   The first convolution reads the (n,3,H,W) NCHW frames of pred and ref directly (one batch of 2n images, so the weights are read
-//   once per layer); its prologue maps the pixel (the evaluator's three modes, as load_mapped of eval.hip) and applies LPIPS's
+//   once per layer); its prologue maps the pixel (the evaluator's three modes, map_pixel of pixel.h) and applies LPIPS's
 //   scaling layer (x - shift) / scale, every step a separately rounded fp32 operation (the file is built without fp contraction).
 //   Padding applies AFTER the scaling: a padded tap contributes 0.
 //
-//   lpips_maxpool_kernel: F.max_pool2d(3, 2), floor mode, NHWC: rows and columns that no window covers are ignored.
+//   maxpool3s2_kernel (maxpool.h) at floor-mode sizes: F.max_pool2d(3, 2), NHWC: rows and columns that no window covers are ignored.
 //
 //   lpips_distance_kernel: one tap's term of the distance, fused: per pixel s_i = sum_c x_i,c^2, n_i = sqrt(s_i) + 1e-10,
 //   d = sum_c w_c (x_0,c / n_0 - x_1,c / n_1)^2, then the sum of d over the pixels -- all in fp64 from the fp32 features.  16 lanes
@@ -27,38 +27,12 @@
 #include <cstring>
 
 #include "common.h"
+#include "igemm32.h"
+#include "maxpool.h"
+#include "pixel.h"
 
 namespace lwg {
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int BM = 64, BN = 64, BK = 32;
-constexpr int A_PITCH = BK + 1;   // odd pitch: the 32 rows a fragment read touches fall into 32 banks
-constexpr int B_PITCH = BN;
-
-// how a stored pixel becomes the value that is scored: the three modes of eval.hip's load_mapped, restated (that file's results
-// must not move, so nothing is shared with it); every step a separately rounded float32 operation
-//   0: as it is   1: [0,1] -> [-1,1], 2*x - 1   2: [-1,1] through the writer's 8 bits and the loader's way back
-__device__ __forceinline__ float map_pixel(float x, int mode)
-{
-    if (mode == 1) {
-        const float t = 2.f * x;
-        return t - 1.f;
-    }
-    if (mode == 2) {
-        const float a = x + 1.f;
-        const float b = a / 2.f;
-        const float c = b * 255.f;
-        float u = truncf(c);
-        u = u > 0.f ? u : 0.f;         // NaN -> 0 as well
-        u = u < 255.f ? u : 255.f;
-        const float d = u / 255.f;
-        const float e = d * 2.f;
-        return e - 1.f;
-    }
-    return x;
-}
 
 // LPIPS's ScalingLayer: (x - shift) / scale per colour channel, a subtraction and a true division
 __device__ __forceinline__ float scale_pixel(float v, int c)
@@ -71,160 +45,50 @@ __device__ __forceinline__ float scale_pixel(float v, int c)
 
 enum { IN_NHWC4 = 0, IN_NHWC = 1, IN_IMAGE = 2 };
 
-struct ConvP {
-    const float *x;          // NHWC (N,H,W,Cin); IN_IMAGE: images 0 .. split-1 as (split,3,H,W) NCHW
-    const float *x2;         // IN_IMAGE: images split .. N-1, NCHW
-    const float *w;          // (k*k*Cin, Cout): [tap][ci][co]
+// the five convolutions: bias + ReLU in the epilogue, as a policy of igemm32::conv_kernel; LpipsFrames, LpipsNhwc4 and LpipsNhwc add
+// the gather
+struct LpipsConv {
+    igemm32::Geom g;
+    const float *x;          // NHWC (N,H,W,Cin); LpipsFrames: images 0 .. split-1 as (split,3,H,W) NCHW
+    const float *x2;         // LpipsFrames: images split .. N-1, NCHW
     const float *bias;       // (Cout) or NULL
     float *y;                // (N,Ho,Wo,Cout)
-    int N, split, H, W, Cin, Cout, ks, stride, pad, Ho, Wo, relu, mode;
-    long M;                  // N*Ho*Wo
-    int K;                   // ks*ks*Cin
+    int split, relu, mode;
+    static constexpr bool kCoutTail = false;
+
+    __device__ float column(int co) const { return bias ? bias[co] : 0.f; }
+    __device__ void write(long m, int co, float b, float v) const
+    {
+        if (bias) v += b;
+        if (relu) v = fmaxf(v, 0.f);
+        y[(size_t)m * g.Cout + co] = v;
+    }
 };
 
-// KIND: IN_NHWC4 -- Cin % 4 == 0, four consecutive reduction indices are one 16-byte load inside one tap; IN_NHWC -- any Cin;
-// IN_IMAGE -- Cin == 3, NCHW frames through map_pixel and scale_pixel
-template <int KIND>
-__global__ __launch_bounds__(256) void lpips_conv_kernel(const ConvP p)
-{
-    __shared__ __attribute__((aligned(16))) float sA[2][BM * A_PITCH];
-    __shared__ __attribute__((aligned(16))) float sB[2][BK * B_PITCH];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const long m0 = (long)blockIdx.x * BM;
-    const int co0 = blockIdx.y * BN;
-
-    // A loader: rows (tid >> 3) and (tid >> 3) + 32, reduction indices (tid & 7) * 4 .. + 3 of the stage
-    const int a_col = (tid & 7) * 4;
-    int a_ih0[2], a_iw0[2];
-    const float *a_base[2];
-    bool a_ok[2];
-#pragma unroll
-    for (int v = 0; v < 2; ++v) {
-        const long m = m0 + (tid >> 3) + 32 * v;
-        a_ok[v] = m < p.M;
-        const long mm = a_ok[v] ? m : 0;
-        const int n = (int)(mm / ((long)p.Ho * p.Wo));
-        const int rem = (int)(mm - (long)n * p.Ho * p.Wo);
-        const int oh = rem / p.Wo, ow = rem - oh * p.Wo;
-        a_ih0[v] = oh * p.stride - p.pad;
-        a_iw0[v] = ow * p.stride - p.pad;
-        const size_t image = (size_t)p.H * p.W * p.Cin;
-        if (KIND == IN_IMAGE) a_base[v] = n < p.split ? p.x + (size_t)n * image : p.x2 + (size_t)(n - p.split) * image;
-        else a_base[v] = p.x + (size_t)n * image;
+// Cin == 3, NCHW frames through map_pixel and scale_pixel
+struct LpipsFrames : LpipsConv {
+    __device__ float4 gather(const igemm32::Row &r, int kg) const
+    {
+        const size_t image = (size_t)g.H * g.W * g.Cin;
+        const float *base = r.n < split ? x + (size_t)r.n * image : x2 + (size_t)(r.n - split) * image;
+        return igemm32::gather_each(g, r, kg, g.Cin, [&](int c, int ih, int iw) {
+            return scale_pixel(map_pixel(base[((size_t)c * g.H + ih) * g.W + iw], mode), c);
+        });
     }
-    // B loader: reduction rows (tid >> 4) and (tid >> 4) + 16, output channels (tid & 15) * 4 .. + 3
-    const int b_col = (tid & 15) * 4;
+};
 
-    float4 ra[2], rb[2];
-    auto gather1 = [&](int v, int kg) -> float {   // one input value; 0 outside the image, past K or past M
-        if (!a_ok[v] || kg >= p.K) return 0.f;
-        const int tap = kg / p.Cin, c = kg - tap * p.Cin;
-        const int kh = tap / p.ks, kw = tap - kh * p.ks;
-        const int ih = a_ih0[v] + kh, iw = a_iw0[v] + kw;
-        if ((unsigned)ih >= (unsigned)p.H || (unsigned)iw >= (unsigned)p.W) return 0.f;
-        if (KIND == IN_IMAGE) return scale_pixel(map_pixel(a_base[v][((size_t)c * p.H + ih) * p.W + iw], p.mode), c);
-        return a_base[v][((size_t)ih * p.W + iw) * p.Cin + c];
-    };
-    auto load = [&](int k0) {
-        const int kg = k0 + a_col;
-#pragma unroll
-        for (int v = 0; v < 2; ++v) {
-            if (KIND == IN_NHWC4) {
-                ra[v] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (a_ok[v] && kg < p.K) {
-                    const int tap = kg / p.Cin, c = kg - tap * p.Cin;
-                    const int kh = tap / p.ks, kw = tap - kh * p.ks;
-                    const int ih = a_ih0[v] + kh, iw = a_iw0[v] + kw;
-                    if ((unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W)
-                        ra[v] = *reinterpret_cast<const float4 *>(a_base[v] + ((size_t)ih * p.W + iw) * p.Cin + c);
-                }
-            } else {
-                ra[v] = make_float4(gather1(v, kg), gather1(v, kg + 1), gather1(v, kg + 2), gather1(v, kg + 3));
-            }
-        }
-#pragma unroll
-        for (int v = 0; v < 2; ++v) {
-            const int kr = k0 + (tid >> 4) + 16 * v;
-            rb[v] = kr < p.K ? *reinterpret_cast<const float4 *>(p.w + (size_t)kr * p.Cout + co0 + b_col)
-                             : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    auto store = [&](int buf) {
-#pragma unroll
-        for (int v = 0; v < 2; ++v) {
-            float *d = &sA[buf][((tid >> 3) + 32 * v) * A_PITCH + a_col];
-            d[0] = ra[v].x;
-            d[1] = ra[v].y;
-            d[2] = ra[v].z;
-            d[3] = ra[v].w;
-            *reinterpret_cast<float4 *>(&sB[buf][((tid >> 4) + 16 * v) * B_PITCH + b_col]) = rb[v];
-        }
-    };
+// Cin % 4 == 0, four consecutive reduction indices are one 16-byte load inside one tap
+struct LpipsNhwc4 : LpipsConv {
+    __device__ float4 gather(const igemm32::Row &r, int kg) const { return igemm32::gather_nhwc4(g, x, r, kg); }
+};
 
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-
-    int buf = 0;
-    load(0);
-    store(0);
-    __syncthreads();
-    for (int k0 = 0; k0 < p.K; k0 += BK) {
-        const bool more = k0 + BK < p.K;
-        if (more) load(k0 + BK);
-        // A: lane -> pixel row (lane & 31), k = lane >> 5;  B: lane -> output channel (lane & 31), k = lane >> 5
-        const float *ar = &sA[buf][(wm * 32 + (lane & 31)) * A_PITCH + (lane >> 5)];
-        const float *br = &sB[buf][(lane >> 5) * B_PITCH + wn * 32 + (lane & 31)];
-#pragma unroll
-        for (int kk = 0; kk < BK / 2; ++kk)
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ar[2 * kk], br[2 * kk * B_PITCH], acc, 0, 0, 0);
-        if (more) store(buf ^ 1);
-        __syncthreads();
-        buf ^= 1;
+// any Cin
+struct LpipsNhwc : LpipsConv {
+    __device__ float4 gather(const igemm32::Row &r, int kg) const
+    {
+        return igemm32::gather_each(g, r, kg, g.Cin, [&](int c, int ih, int iw) { return *igemm32::nhwc_at(g, x, r, c, ih, iw); });
     }
-
-    // C/D layout: col = lane & 31 -> output channel, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5) -> pixel
-    const int co = co0 + wn * 32 + (lane & 31);
-    const float bias = p.bias ? p.bias[co] : 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const long m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        if (m >= p.M) continue;
-        float v = acc[r];
-        if (p.bias) v += bias;
-        if (p.relu) v = fmaxf(v, 0.f);
-        p.y[(size_t)m * p.Cout + co] = v;
-    }
-}
-
-// max_pool2d(kernel 3, stride 2), floor mode, no padding, NHWC, C % 4 == 0: every window lies inside the input
-__global__ __launch_bounds__(256) void lpips_maxpool_kernel(const float *__restrict__ x, int H, int W, int C4, int Ho, int Wo,
-                                                           long total, float *__restrict__ y)
-{
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;   // over N*Ho*Wo*C4
-    if (i >= total) return;
-    const int c4 = (int)(i % C4);
-    long px = i / C4;
-    const int ow = (int)(px % Wo);
-    px /= Wo;
-    const int oh = (int)(px % Ho);
-    const long n = px / Ho;
-    const float4 *xs = reinterpret_cast<const float4 *>(x);
-    float4 m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-#pragma unroll
-    for (int kh = 0; kh < 3; ++kh) {
-#pragma unroll
-        for (int kw = 0; kw < 3; ++kw) {
-            const float4 v = xs[((n * H + (oh * 2 + kh)) * W + (ow * 2 + kw)) * C4 + c4];
-            m.x = fmaxf(m.x, v.x);
-            m.y = fmaxf(m.y, v.y);
-            m.z = fmaxf(m.z, v.z);
-            m.w = fmaxf(m.w, v.w);
-        }
-    }
-    reinterpret_cast<float4 *>(y)[i] = m;
-}
+};
 
 constexpr int kDistThreads = 1024, kDistLanes = 16, kChunk = kDistThreads / kDistLanes;   // 64 pixels per chunk
 constexpr int kTaps = 5;
@@ -339,30 +203,19 @@ bool conv_geometry_ok(int k, int stride, int pad)
     return (k == 11 && stride == 4 && pad == 2) || (k == 5 && stride == 1 && pad == 2) || (k == 3 && stride == 1 && pad == 1);
 }
 
-inline int conv_out(int in, const Layer &l) { return (in + 2 * l.pad - l.ks) / l.stride + 1; }
-inline int pool_out(int in) { return (in - 3) / 2 + 1; }
+inline int conv_out(int in, const Layer &l) { return igemm32::conv_out(in, l.ks, l.stride, l.pad); }
 
-int launch_conv(ConvP p, int kind, hipStream_t st)
+int launch_conv(const LpipsConv &p, int kind, hipStream_t st)
 {
-    p.Ho = (p.H + 2 * p.pad - p.ks) / p.stride + 1;
-    p.Wo = (p.W + 2 * p.pad - p.ks) / p.stride + 1;
-    p.M = (long)p.N * p.Ho * p.Wo;
-    p.K = p.ks * p.ks * p.Cin;
-    const dim3 grid((unsigned)ceil_div(p.M, BM), (unsigned)(p.Cout / BN));
-    if (kind == IN_IMAGE) lpips_conv_kernel<IN_IMAGE><<<grid, 256, 0, st>>>(p);
-    else if (kind == IN_NHWC4) lpips_conv_kernel<IN_NHWC4><<<grid, 256, 0, st>>>(p);
-    else lpips_conv_kernel<IN_NHWC><<<grid, 256, 0, st>>>(p);
-    LWG_LAUNCH_CHECK("lpips_conv_kernel");
-    return LWG_OK;
+    if (kind == IN_IMAGE) return igemm32::launch(LpipsFrames{p}, "igemm32::conv_kernel<LpipsFrames>", st);
+    if (kind == IN_NHWC4) return igemm32::launch(LpipsNhwc4{p}, "igemm32::conv_kernel<LpipsNhwc4>", st);
+    return igemm32::launch(LpipsNhwc{p}, "igemm32::conv_kernel<LpipsNhwc>", st);
 }
 
-int launch_maxpool(const float *x, int N, int H, int W, int C, float *y, hipStream_t st)
+// F.max_pool2d(3, 2), floor mode: rows and columns that no window covers are ignored
+int launch_floor_maxpool(const float *x, int N, int H, int W, int C, float *y, hipStream_t st)
 {
-    const int Ho = pool_out(H), Wo = pool_out(W);
-    const long total = (long)N * Ho * Wo * (C / 4);
-    lpips_maxpool_kernel<<<ceil_div(total, 256), 256, 0, st>>>(x, H, W, C / 4, Ho, Wo, total, y);
-    LWG_LAUNCH_CHECK("lpips_maxpool_kernel");
-    return LWG_OK;
+    return launch_maxpool(x, N, H, W, C, pool_out(H), pool_out(W), y, C, 0, st);
 }
 
 inline int chunks_of(long P) { return ceil_div(P, kChunk); }
@@ -376,7 +229,7 @@ int launch_distance(const float *f0, const float *f1, int n, int P, int C, const
     return LWG_OK;
 }
 
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+using igemm32::aligned16;
 
 }  // namespace
 }  // namespace lwg
@@ -431,19 +284,18 @@ int lwg_lpips_create(lwg_lpips **out, int max_pairs, int max_h, int max_w)
     h->max_h = max_h;
     h->max_w = max_w;
     build_plan(h);
-    auto alloc = [&](float **p, size_t n) { return hipMalloc(reinterpret_cast<void **>(p), n * sizeof(float)); };
-    hipError_t e = alloc(&h->blob, h->blob_floats);
+    hipError_t e = alloc_floats(&h->blob, h->blob_floats);
     int H = max_h, W = max_w, npool = 0;
     long chunks = 0;
     for (int l = 0; l < kTaps && e == hipSuccess; ++l) {
         H = conv_out(H, kLayers[l]);
         W = conv_out(W, kLayers[l]);
         chunks += chunks_of((long)H * W);
-        e = alloc(&h->feat[l], (size_t)2 * max_pairs * H * W * kLayers[l].Cout);
+        e = alloc_floats(&h->feat[l], (size_t)2 * max_pairs * H * W * kLayers[l].Cout);
         if (kLayers[l].pool && e == hipSuccess) {
             H = pool_out(H);
             W = pool_out(W);
-            e = alloc(&h->pooled[npool++], (size_t)2 * max_pairs * H * W * kLayers[l].Cout);
+            e = alloc_floats(&h->pooled[npool++], (size_t)2 * max_pairs * H * W * kLayers[l].Cout);
         }
     }
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&h->taps), (size_t)max_pairs * kTaps * sizeof(double));
@@ -459,13 +311,12 @@ int lwg_lpips_create(lwg_lpips **out, int max_pairs, int max_h, int max_w)
 void lwg_lpips_destroy(lwg_lpips *h)
 {
     if (!h) return;
-    auto fr = [](void *p) { if (p) (void)hipFree(p); };
-    fr(h->blob);
-    for (int l = 0; l < kTaps; ++l) fr(h->feat[l]);
-    fr(h->pooled[0]);
-    fr(h->pooled[1]);
-    fr(h->taps);
-    fr(h->partial);
+    free_device(h->blob);
+    for (int l = 0; l < kTaps; ++l) free_device(h->feat[l]);
+    free_device(h->pooled[0]);
+    free_device(h->pooled[1]);
+    free_device(h->taps);
+    free_device(h->partial);
     delete h;
 }
 
@@ -476,12 +327,7 @@ int lwg_lpips_set_weights(lwg_lpips *h, const float *blob_host, size_t n_floats)
     LWG_REQUIRE(h != nullptr, "lwg_lpips_set_weights: NULL handle");
     LWG_REQUIRE(blob_host != nullptr, "lwg_lpips_set_weights: NULL blob");
     LWG_REQUIRE(n_floats == h->blob_floats, "lwg_lpips_set_weights: blob of %zu floats, this network takes %zu", n_floats, h->blob_floats);
-    h->ready = false;
-    // synchronous: the caller's host buffer may go away after the call, and no forward may overlap the replacement
-    LWG_HIP(hipDeviceSynchronize());
-    LWG_HIP(hipMemcpy(h->blob, blob_host, n_floats * sizeof(float), hipMemcpyHostToDevice));
-    h->ready = true;
-    return LWG_OK;
+    return upload_blob(h->blob, blob_host, n_floats, h->ready);
 }
 
 int lwg_lpips_forward(lwg_lpips *h, const float *pred, const float *ref, int n, int H, int W, int mode, double *dist, double *taps,
@@ -506,15 +352,14 @@ int lwg_lpips_forward(lwg_lpips *h, const float *pred, const float *ref, int n, 
     long off = 0;
     for (int l = 0; l < kTaps; ++l) {
         const Layer &L = kLayers[l];
-        ConvP p;
+        LpipsConv p;
         memset(&p, 0, sizeof(p));
+        p.g = igemm32::geom(h->blob + h->w_off[l], 2 * n, ch, cw, L.Cin, L.Cout, L.ks, L.ks, L.stride, L.pad, L.pad);
         p.x = l == 0 ? pred : src;
         p.x2 = l == 0 ? ref : nullptr;
-        p.w = h->blob + h->w_off[l];
         p.bias = h->blob + h->b_off[l];
         p.y = h->feat[l];
-        p.N = 2 * n; p.split = n; p.H = ch; p.W = cw; p.Cin = L.Cin; p.Cout = L.Cout; p.ks = L.ks; p.stride = L.stride; p.pad = L.pad;
-        p.relu = 1; p.mode = mode;
+        p.split = n; p.relu = 1; p.mode = mode;
         int rc = launch_conv(p, l == 0 ? IN_IMAGE : IN_NHWC4, st);
         if (rc != LWG_OK) return rc;
         ch = conv_out(ch, L);
@@ -529,7 +374,7 @@ int lwg_lpips_forward(lwg_lpips *h, const float *pred, const float *ref, int n, 
         off += (long)n * tp.chunks[l];
         src = h->feat[l];
         if (L.pool) {
-            rc = launch_maxpool(h->feat[l], 2 * n, ch, cw, L.Cout, h->pooled[npool], st);
+            rc = launch_floor_maxpool(h->feat[l], 2 * n, ch, cw, L.Cout, h->pooled[npool], st);
             if (rc != LWG_OK) return rc;
             src = h->pooled[npool++];
             ch = pool_out(ch);
@@ -556,17 +401,16 @@ int lwg_lpips_conv(const float *x, int N, int H, int W, int Cin, const float *w,
     LWG_REQUIRE(input_mode >= 0 || Cin % 4 != 0 || aligned16(x), "lwg_lpips_conv: x is not 16-byte aligned");
     if (!conv_geometry_ok(k, stride, pad))
         LWG_FAIL(LWG_ERR_UNSUPPORTED, "lwg_lpips_conv: (k, stride, pad) = (%d, %d, %d) is none of (11,4,2) (5,1,2) (3,1,1)", k, stride, pad);
-    if (Cout % lwg::BN != 0) LWG_FAIL(LWG_ERR_UNSUPPORTED, "lwg_lpips_conv: Cout = %d is no multiple of %d", Cout, lwg::BN);
-    if ((long)N * H * W * (long)(Cin > Cout ? Cin : Cout) >= (1L << 40)) LWG_FAIL(LWG_ERR_UNSUPPORTED, "lwg_lpips_conv: tensor too large");
-    const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
-    LWG_REQUIRE(H + 2 * pad >= k && W + 2 * pad >= k && Ho >= 1 && Wo >= 1, "lwg_lpips_conv: empty output");
-    if ((long)k * k * Cin > 0x7fffffffL || ((long)N * Ho * Wo + lwg::BM - 1) / lwg::BM > 0x7fffffffL)
-        LWG_FAIL(LWG_ERR_UNSUPPORTED, "lwg_lpips_conv: tensor too large");
-    ConvP p;
+    if (Cout % igemm32::BN != 0) LWG_FAIL(LWG_ERR_UNSUPPORTED, "lwg_lpips_conv: Cout = %d is no multiple of %d", Cout, igemm32::BN);
+    if (igemm32::too_large(N, H, W, Cin > Cout ? Cin : Cout)) LWG_FAIL(LWG_ERR_UNSUPPORTED, "lwg_lpips_conv: tensor too large");
+    const int Ho = igemm32::conv_out(H, k, stride, pad), Wo = igemm32::conv_out(W, k, stride, pad);
+    LWG_REQUIRE(Ho >= 1 && Wo >= 1, "lwg_lpips_conv: empty output");
+    if (igemm32::grid_too_large(N, Ho, Wo, k, k, Cin)) LWG_FAIL(LWG_ERR_UNSUPPORTED, "lwg_lpips_conv: tensor too large");
+    LpipsConv p;
     memset(&p, 0, sizeof(p));
-    p.x = x; p.x2 = x; p.w = w; p.bias = bias; p.y = y;
-    p.N = N; p.split = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.ks = k; p.stride = stride; p.pad = pad;
-    p.relu = relu; p.mode = input_mode < 0 ? 0 : input_mode;
+    p.g = igemm32::geom(w, N, H, W, Cin, Cout, k, k, stride, pad, pad);
+    p.x = x; p.x2 = x; p.bias = bias; p.y = y;
+    p.split = N; p.relu = relu; p.mode = input_mode < 0 ? 0 : input_mode;
     return launch_conv(p, input_mode >= 0 ? IN_IMAGE : (Cin % 4 == 0 ? IN_NHWC4 : IN_NHWC), as_stream(stream));
 }
 
@@ -577,7 +421,7 @@ int lwg_lpips_maxpool(const float *x, int N, int H, int W, int C, float *y, lwg_
     if (C % 4 != 0) LWG_FAIL(LWG_ERR_UNSUPPORTED, "lwg_lpips_maxpool: C = %d is no multiple of 4", C);
     LWG_REQUIRE(aligned16(x) && aligned16(y), "lwg_lpips_maxpool: x / y are not 16-byte aligned");
     if ((long)N * pool_out(H) * pool_out(W) * (C / 4) > 256L * 0x7fffffffL) LWG_FAIL(LWG_ERR_UNSUPPORTED, "lwg_lpips_maxpool: tensor too large");
-    return launch_maxpool(x, N, H, W, C, y, as_stream(stream));
+    return launch_floor_maxpool(x, N, H, W, C, y, as_stream(stream));
 }
 
 int lwg_lpips_layer_distance(const float *f0, const float *f1, int n, int P, int C, const float *w, double *out, lwg_stream_t stream)

@@ -119,7 +119,7 @@ def main():
             model(x, mode=1)
         torch.cuda.synchronize()
     ev = sorted((k for k in prof.events() if k.device_type == DeviceType.CUDA), key=lambda k: k.time_range.start)
-    ev = [k for k in ev if "inception_" in k.name]
+    ev = [k for k in ev if "lwg" in k.name]
     assert len(ev) == reps * per_forward, "expected %d kernels per forward, the profiler saw %d in %d forwards" % (per_forward, len(ev), reps)
     us = [sum(ev[r * per_forward + k].time_range.elapsed_us() for r in range(reps)) / reps for k in range(per_forward)]
     dev_us, k = [], 1
